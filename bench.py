@@ -23,6 +23,11 @@ One JSON line on rank 0, with `roofline` (dominant kernel, HIP events on the lib
                   from host arrays;
   `secondary.c5`  the top-N scoring path (BASELINE config 5: all 1M users x 200K items, the factors the timed epochs left)
                   with its own roofline (MFMA) and CPU baseline.
+
+`--dump-outputs DIR` writes what the last timed step computed (rank 0) as DIR/<name>.npy, float32 / float64, 64 MB at most:
+the factors the epoch left and its (nll, sum P*P, sum Q*Q); the top-N lists of the scoring workloads; FISM's model.  Outputs
+larger than that are a fixed seeded sample of their rows, named in the *_index arrays.  The inputs are seeded, so two builds
+run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -69,6 +74,33 @@ MFMA_F32_PEAK = 157.3e12   # dense f32-input MFMA, MI355X (MI355X_MICROARCH.md)
 MFMA_BF16_PEAK = 2.5e15    # dense bf16 MFMA
 LR, REG_U, REG_I = 0.02, 0.01, 0.01
 HBM_PEAK = 8.0e12          # B/s, MI355X spec (MI355X_MICROARCH.md)
+
+
+DUMP_LIMIT = 64 << 20      # --dump-outputs: bytes of all arrays together
+DUMP_SEED = 20260099       # the fixed sample of rows / users a dump holds when the whole output is larger
+
+
+def dump_rows(n, row_bytes, budget=16 << 20):
+    """--dump-outputs: the rows of an n-row output a dump keeps -- all of them when they fit `budget` bytes,
+    else a fixed seeded sample (ascending), identical from run to run and between builds."""
+    cap = max(1, budget // row_bytes)
+    if n <= cap:
+        return np.arange(n)
+    return np.sort(np.random.RandomState(DUMP_SEED).choice(n, cap, replace=False))
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as path/<name>.npy, float32 kept, anything else as float64; 64 MB at most in all."""
+    out = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        out[name] = np.ascontiguousarray(a if a.dtype in (np.float32, np.float64) else a.astype(np.float64))
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT:
+        sys.exit('--dump-outputs: %d bytes exceed the limit of %d' % (total, DUMP_LIMIT))
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + '.npy'), a)
 
 
 def algorithmic_bytes(k):
@@ -408,6 +440,10 @@ def bench_scoring(args, cp):
         kms += ms
     cp.barrier()
     dt = cp.reduce_max(time.perf_counter() - t0)
+    if cp.rank == 0 and args.dump_outputs:
+        # the last timed scan's lists of this rank's users
+        sel = dump_rows(len(users), N * (ids.itemsize * 2 + sc.itemsize))
+        dump_outputs(args.dump_outputs, {'user_index': users[sel], 'topn_ids': ids[sel], 'topn_scores': sc[sel]})
     cpu = None
     if cp.rank == 0 and cp.world == 1 and not args.no_cpu_baseline:
         cpu = scoring_cpu_baseline(dev, data, users, ids, N, n, 12.0)
@@ -467,8 +503,17 @@ def bench_fism(args, cp):
         dev.fism_rounds(ptr, ev_i, negs[e], rho, coef, round_users, lr, reg, reg)
     t0 = time.perf_counter()
     for e in range(args.warmup, args.warmup + args.steps):
-        half = dev.fism_rounds(ptr, ev_i, negs[e], rho, coef, round_users, lr, reg, reg)[0]
+        sums = dev.fism_rounds(ptr, ev_i, negs[e], rho, coef, round_users, lr, reg, reg)
     dt = time.perf_counter() - t0
+    half = sums[0]
+    if args.dump_outputs:
+        # the model after the last timed epoch and that epoch's (half squared error, sum P*P, sum Q*Q, Bi.Bi)
+        Pm, Qm, Bm = np.empty((n, k), np.float64), np.empty((n, k), np.float32), np.empty(n, np.float64)
+        dev.fism_get_model(Pm, Qm, Bm)
+        rows = dump_rows(n, k * 8)
+        dump_outputs(args.dump_outputs, {'fism_sums': np.array(sums, np.float64), 'item_index': rows,
+                                         'P_rows': Pm[rows], 'Q_rows': Qm[rows], 'Bi_rows': Bm[rows]})
+        del Pm, Qm, Bm
     # the sequential device pass and the NumPy loop on the first users of the same problem
     su = min(m, 2000)
     sl = slice(0, int(ptr[su]))
@@ -516,7 +561,12 @@ def main():
     ap.add_argument('--tpw', type=int, default=0, help='tuning: events per wave in the round kernel (0 = default)')
     ap.add_argument('--opt', action='append', default=[], metavar='NAME=VALUE', help='tuning: yue_set_option(NAME, VALUE), repeatable')
     ap.add_argument('--force-comm', action='store_true', help='N=1 only: run the communicator code path with a 1-rank RCCL communicator')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what the last timed step computed as DIR/<name>.npy (float32 / float64, '
+                         '64 MB at most: a fixed seeded sample of rows when the output is larger)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
 
     cp = ControlPlane()
     rank, world, local_rank = cp.rank, cp.world, cp.local_rank
@@ -587,6 +637,14 @@ def main():
     comm = dev.comm_stats()
     if not np.isfinite(nll):
         sys.exit('loss is not finite')
+
+    if rank == 0 and args.dump_outputs:
+        # the factors the last timed epoch left (users replicated, this rank's item shard) and its (nll, sum P*P, sum Q*Q)
+        P, Q = dev.get_factors()
+        pu, qi = dump_rows(m, k * 4), dump_rows(n, k * 4)
+        dump_outputs(args.dump_outputs, {'epoch_sums': np.array([nll, sp, sq], np.float64),
+                                         'P_row_index': pu, 'P_rows': P[pu], 'Q_row_index': qi, 'Q_rows': Q[qi]})
+        del P, Q
 
     if rank == 0:
         total = float(E) * world * args.steps
