@@ -261,6 +261,26 @@ int yue_fism_rounds(yue_ctx *ctx, const int64_t *user_ptr, int64_t m, const int3
 int yue_fism_scores(yue_ctx *ctx, const int32_t *items, int64_t n_items, double *out_n);
 int yue_fism_topn_scan(yue_ctx *ctx, const int64_t *row_ptr, const int32_t *row_items, int64_t nu, int N, int32_t *out_ids, double *out_scores);
 
+/*
+ * WRMF (reference recommender/cf/WRMF.py; Hu, Koren and Volinsky's implicit-feedback MF) -- ALS half-sweeps on the
+ * context's factors: X = P (users), Y = Q (items), as uploaded by yue_set_factors, so yue_scores / yue_topn_scan rank
+ * with X and Y unchanged.  Needs 1 <= k <= 128 (larger k: YUE_ERR_ARG, nothing launched).
+ *   yue_wrmf_set_pairs  the distinct (user, item) pairs both ways with their event counts r >= 1: user-major (u_ptr[m+1],
+ *                    items ascending within a user) and item-major (i_ptr[n+1], users ascending), the transpose of each
+ *                    other; sizes are those of yue_set_factors.  Builds the longest-row-first solve schedule and the
+ *                    chunks of the long rows (option "wrmf_long_pairs", default 2048 pairs).
+ *   yue_wrmf_half_sweep side 0: every X[u] from Y; side 1: every Y[i] from X.  Per row, over its pairs f_j with counts r_j:
+ *                    A = fp32(F^T F) + sum alpha*r_j f_j f_j^T + reg*I,  b = sum (1 + alpha*r_j) f_j,  x = A^-1 b by an fp64
+ *                    Cholesky factorisation, rounded to fp32 once; rows without pairs become 0.  loss_out (side 0, may be
+ *                    NULL): sum over the pairs of (1 - x_old . y)^2, the dot rounded to fp32, the sum in fp64.  A
+ *                    non-positive pivot returns YUE_ERR_ARG naming the (smallest such) row.  Bit-reproducible (no float
+ *                    atomics).  Read-only options: "wrmf_last_ns" / "wrmf_last_long_ns" (device time of the last half-sweep /
+ *                    of its long-row chunks), "wrmf_long_rows_user" / "wrmf_long_rows_item".
+ */
+int yue_wrmf_set_pairs(yue_ctx *ctx, const int64_t *u_ptr, const int32_t *u_items, const int32_t *u_counts,
+                       const int64_t *i_ptr, const int32_t *i_users, const int32_t *i_counts, int64_t nnz);
+int yue_wrmf_half_sweep(yue_ctx *ctx, int side, double alpha, double reg, double *loss_out);
+
 /* Multi-GPU (one process per GPU, RCCL over xGMI).  Rank 0 creates the id, the caller ships
  * the 128 bytes to the other ranks (any side channel), every rank calls yue_comm_init. */
 int yue_comm_unique_id(void *id128_out);

@@ -24,7 +24,8 @@ SYMBOLS = ['yue_last_error', 'yue_version', 'yue_ctx_create', 'yue_ctx_destroy',
            'yue_topn_scan', 'yue_set_kernel_timing', 'yue_get_kernel_timing', 'yue_get_scan_stats', 'yue_get_scan_work', 'yue_set_option', 'yue_get_option',
            'yue_comm_unique_id', 'yue_comm_init', 'yue_allreduce_f64', 'yue_get_comm_stats',
            'yue_default_round_events', 'yue_epoch_plan',
-           'yue_fism_set_model', 'yue_fism_get_model', 'yue_fism_epoch', 'yue_fism_rounds', 'yue_fism_scores', 'yue_fism_topn_scan']
+           'yue_fism_set_model', 'yue_fism_get_model', 'yue_fism_epoch', 'yue_fism_rounds', 'yue_fism_scores', 'yue_fism_topn_scan',
+           'yue_wrmf_set_pairs', 'yue_wrmf_half_sweep']
 
 
 class YueHipError(RuntimeError):
@@ -330,6 +331,29 @@ class Device(object):
             raise IndexError(self._lib.yue_last_error().decode())
         self._chk(rc)
         return ids, sc
+
+    # -- WRMF (ALS half-sweeps on the factors of set_factors) ----------------------------------
+    def wrmf_set_pairs(self, u_ptr, u_items, u_counts, i_ptr, i_users, i_counts):
+        """Distinct pairs both ways with their counts: user-major (items ascending) and item-major (users ascending)."""
+        u_ptr, a = _i64(u_ptr)
+        i_ptr, d = _i64(i_ptr)
+        assert len(u_ptr) == self.m + 1 and len(i_ptr) == self.n + 1, 'wrmf_set_pairs: pointer sizes must match set_factors (m + 1, n + 1)'
+        nnz = int(u_ptr[-1])
+        assert int(i_ptr[-1]) == nnz and len(u_items) == nnz and len(u_counts) == nnz and len(i_users) == nnz and len(i_counts) == nnz, \
+            'wrmf_set_pairs: both directions must hold nnz pairs'
+        u_items, b = _i32(u_items if nnz else np.zeros(1, np.int32))
+        u_counts, c = _i32(u_counts if nnz else np.zeros(1, np.int32))
+        i_users, e = _i32(i_users if nnz else np.zeros(1, np.int32))
+        i_counts, f = _i32(i_counts if nnz else np.zeros(1, np.int32))
+        self._chk(self._lib.yue_wrmf_set_pairs(self._ctx, a, b, c, d, e, f, C.c_int64(nnz)))
+
+    def wrmf_half_sweep(self, side, alpha, reg):
+        """side 0: every user row from the item factors (returns the loss over the pairs, from the rows before the sweep);
+        side 1: every item row from the user factors (returns 0.0)."""
+        assert side in (0, 1)
+        loss = C.c_double()
+        self._chk(self._lib.yue_wrmf_half_sweep(self._ctx, C.c_int(side), C.c_double(alpha), C.c_double(reg), C.byref(loss)))
+        return loss.value
 
     def comm_init(self, unique_id, rank, nranks):
         buf = (C.c_ubyte * UNIQUE_ID_BYTES).from_buffer_copy(unique_id)

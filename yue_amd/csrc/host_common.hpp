@@ -3,6 +3,7 @@
 //   core_host.hip   context, factors, interactions            bpr_host.hip   replay levels, S-rounds, epochs, CUNE, Adam, options
 //   chain_host.hip  exact sequential semantics as dataflow    scan_host.hip  predict + evalRanking's selection
 //   fism_host.hip   FISM                                      comm.hip       RCCL
+//   wrmf_host.hip   WRMF (ALS half-sweeps)
 #pragma once
 #include "../../include/yue_hip.h"
 
@@ -17,6 +18,7 @@
 #include <vector>
 
 struct ncclComm;
+struct yue_wrmf;                                     // wrmf_host.hip: pairs, schedules, workspaces of the WRMF half-sweeps
 
 namespace yue_host {
 
@@ -180,6 +182,7 @@ struct yue_ctx {
     double comm_bytes = 0.0, comm_wait_ms = 0.0;
     int comm_version = 0, comm_nranks_reported = 0;
     hipEvent_t ev_scan0 = nullptr, ev_scan1 = nullptr;      // brackets of the scoring kernel (yue_get_scan_stats)
+    yue_wrmf *wrmf = nullptr;            // WRMF state (yue_wrmf_set_pairs), owned by wrmf_host.hip
 };
 
 namespace yue_host {
@@ -194,4 +197,8 @@ int reduce_user_block(yue_ctx *c, int64_t first, int64_t count, hipStream_t stre
 // chain_host.hip: exact sequential semantics over the uploaded events (negatives in ev_j) / over the stream in xu, xi, xj
 int chain_epoch(yue_ctx *c, double lr, double regU, double regI);
 int chain_stream(yue_ctx *c, int64_t T, double lr, double regU, double regI);
+// wrmf_host.hip: frees the WRMF state; options "wrmf_*" (returns 1 when `key` is not one of them)
+void wrmf_release(yue_ctx *c);
+int wrmf_set_option(yue_ctx *c, const std::string &key, int64_t value);
+int wrmf_get_option(yue_ctx *c, const std::string &key, int64_t *value);
 }  // namespace yue_host
