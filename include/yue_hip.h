@@ -281,6 +281,32 @@ int yue_wrmf_set_pairs(yue_ctx *ctx, const int64_t *u_ptr, const int32_t *u_item
                        const int64_t *i_ptr, const int32_t *i_users, const int32_t *i_counts, int64_t nnz);
 int yue_wrmf_half_sweep(yue_ctx *ctx, int side, double alpha, double reg, double *loss_out);
 
+/*
+ * UserKNN (reference recommender/cf/UserKNN.py) -- exact user neighbours and neighbourhood ranking.  Needs no factors.
+ * A_u is the set of distinct training items of user u; sim(u, v) = 2|A_u & A_v| / |A_u | A_v| (not Jaccard: in [0, 2]).
+ *   yue_knn_set_pairs  the distinct (user, item) pairs both ways: user-major (u_ptr[m+1], items ascending within a user,
+ *                    with their event counts >= 1) and item-major (i_ptr[n+1], users ascending), the transpose of each
+ *                    other.  Needs n < 2^26 (similarities are ordered as exact integer ratios).
+ *   yue_knn_neighbors  for every user the first K (1 <= K <= 256) other users with positive similarity by (sim descending,
+ *                    user id ascending), as m x K arrays: neighbour id, |A_u & A_v|, |A_u | A_v|, padded with -1 / 0 / 0
+ *                    behind the positive neighbours; any output may be NULL.  The lists stay on the device for the two
+ *                    calls below.  No m x m matrix: per-row posting-list counting in passes of "knn_range" users.
+ *   yue_knn_predict    the full ranked list of one user: every item some positive neighbour holds, score = sum_r sim_r *
+ *                    count_r(i) / sum_r sim_r over the neighbours in rank order (fp64, no fused multiply-add), ordered by
+ *                    (score descending, item ascending), the user's own items included.  Writes min(len, cap) entries;
+ *                    *len_out = the full length.
+ *   yue_knn_topn       the same lists for `users` without each user's own training items, cut at N (1 <= N <= 100): ids_out /
+ *                    scores_out [nu][N] padded with -1 / 0, len_out[nu] the real lengths (a list may be shorter than N).
+ *                    Neighbour sets of more than "knn_gather" entries are scored in item-range chunks.
+ * Options: "knn_range" (64..4096, candidate users per counting pass), "knn_gather" (256..2048, entries per scoring chunk);
+ * read-only "knn_last_ns" (device time of the last neighbours / topn / predict call), "knn_last_chunked_users".
+ */
+int yue_knn_set_pairs(yue_ctx *ctx, int64_t m, int64_t n, const int64_t *u_ptr, const int32_t *u_items, const int32_t *u_counts,
+                      const int64_t *i_ptr, const int32_t *i_users, int64_t nnz);
+int yue_knn_neighbors(yue_ctx *ctx, int K, int32_t *nbr_out, int32_t *inter_out, int32_t *union_out);
+int yue_knn_predict(yue_ctx *ctx, int32_t user, int64_t cap, int32_t *items_out, double *scores_out, int64_t *len_out);
+int yue_knn_topn(yue_ctx *ctx, const int32_t *users, int64_t nu, int N, int32_t *ids_out, double *scores_out, int32_t *len_out);
+
 /* Multi-GPU (one process per GPU, RCCL over xGMI).  Rank 0 creates the id, the caller ships
  * the 128 bytes to the other ranks (any side channel), every rank calls yue_comm_init. */
 int yue_comm_unique_id(void *id128_out);

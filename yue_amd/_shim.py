@@ -25,7 +25,8 @@ SYMBOLS = ['yue_last_error', 'yue_version', 'yue_ctx_create', 'yue_ctx_destroy',
            'yue_comm_unique_id', 'yue_comm_init', 'yue_allreduce_f64', 'yue_get_comm_stats',
            'yue_default_round_events', 'yue_epoch_plan',
            'yue_fism_set_model', 'yue_fism_get_model', 'yue_fism_epoch', 'yue_fism_rounds', 'yue_fism_scores', 'yue_fism_topn_scan',
-           'yue_wrmf_set_pairs', 'yue_wrmf_half_sweep']
+           'yue_wrmf_set_pairs', 'yue_wrmf_half_sweep',
+           'yue_knn_set_pairs', 'yue_knn_neighbors', 'yue_knn_predict', 'yue_knn_topn']
 
 
 class YueHipError(RuntimeError):
@@ -99,6 +100,7 @@ class Device(object):
         self._raise = raise_errors
         self._ctx = C.c_void_p()
         self.m = self.n = self.k = self.E = 0
+        self.knn_m = self.knn_n = 0
         self._chk(self._lib.yue_ctx_create(C.c_int(device), C.byref(self._ctx)))
 
     # reference convention: print, exit(-1)
@@ -354,6 +356,48 @@ class Device(object):
         loss = C.c_double()
         self._chk(self._lib.yue_wrmf_half_sweep(self._ctx, C.c_int(side), C.c_double(alpha), C.c_double(reg), C.byref(loss)))
         return loss.value
+
+    # -- UserKNN (needs no factors) ------------------------------------------------------------
+    def knn_set_pairs(self, m, n, u_ptr, u_items, u_counts, i_ptr, i_users):
+        """Distinct pairs both ways: user-major (items ascending, with event counts) and item-major (users ascending)."""
+        u_ptr, a = _i64(u_ptr)
+        i_ptr, e = _i64(i_ptr)
+        assert len(u_ptr) == m + 1 and len(i_ptr) == n + 1, 'knn_set_pairs: pointer sizes must be m + 1, n + 1'
+        nnz = int(u_ptr[-1])
+        assert int(i_ptr[-1]) == nnz and len(u_items) == nnz and len(u_counts) == nnz and len(i_users) == nnz, \
+            'knn_set_pairs: both directions must hold nnz pairs'
+        u_items, b = _i32(u_items if nnz else np.zeros(1, np.int32))
+        u_counts, c = _i32(u_counts if nnz else np.zeros(1, np.int32))
+        i_users, f = _i32(i_users if nnz else np.zeros(1, np.int32))
+        self._chk(self._lib.yue_knn_set_pairs(self._ctx, C.c_int64(m), C.c_int64(n), a, b, c, e, f, C.c_int64(nnz)))
+        self.knn_m, self.knn_n = int(m), int(n)
+
+    def knn_neighbors(self, K):
+        """(nbr, inter, union), each int32 [m, K]: the first K positive-similarity users by (sim desc, id asc), -1 / 0 / 0 padded."""
+        out = [np.empty((self.knn_m, max(int(K), 0)), np.int32) for _ in range(3)]
+        ptrs = [o.ctypes.data_as(C.POINTER(C.c_int32)) for o in out]
+        self._chk(self._lib.yue_knn_neighbors(self._ctx, C.c_int(K), *ptrs))
+        return tuple(out)
+
+    def knn_predict(self, user):
+        """(items int32, scores float64): the full list of one user by (score desc, item asc), own items included."""
+        items = np.empty(self.knn_n, np.int32)
+        scores = np.empty(self.knn_n, np.float64)
+        length = C.c_int64()
+        self._chk(self._lib.yue_knn_predict(self._ctx, C.c_int32(int(user)), C.c_int64(self.knn_n), items.ctypes.data_as(C.POINTER(C.c_int32)),
+                                            scores.ctypes.data_as(C.POINTER(C.c_double)), C.byref(length)))
+        return items[:length.value], scores[:length.value]
+
+    def knn_topn(self, users, N):
+        """(ids int32 [nu, N] -1 padded, scores float64 [nu, N] 0 padded, lens int32 [nu]) without each user's own items."""
+        users, up = _i32(users)
+        nu = len(users)
+        ids = np.empty((nu, max(int(N), 0)), np.int32)
+        scores = np.empty((nu, max(int(N), 0)), np.float64)
+        lens = np.empty(nu, np.int32)
+        self._chk(self._lib.yue_knn_topn(self._ctx, up, C.c_int64(nu), C.c_int(N), ids.ctypes.data_as(C.POINTER(C.c_int32)),
+                                         scores.ctypes.data_as(C.POINTER(C.c_double)), lens.ctypes.data_as(C.POINTER(C.c_int32))))
+        return ids, scores, lens
 
     def comm_init(self, unique_id, rank, nranks):
         buf = (C.c_ubyte * UNIQUE_ID_BYTES).from_buffer_copy(unique_id)

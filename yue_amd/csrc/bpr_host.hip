@@ -830,6 +830,7 @@ int yue_get_option(yue_ctx *c, const char *name, int64_t *value) {
     // which kernels yue_bpr_epoch runs for the uploaded factors: 0 k_round, 1 k_round_meta + k_round_m + k_round_fold
     else if (key == "round_path") *value = fold_path(c) ? 1 : 0;
     else if (key.compare(0, 5, "wrmf_") == 0) return yue_host::wrmf_get_option(c, key, value);
+    else if (key.compare(0, 4, "knn_") == 0) return yue_host::knn_get_option(c, key, value);
     else return fail(YUE_ERR_ARG, "yue_get_option: unknown option " + key);
     return YUE_OK;
 }
@@ -897,6 +898,7 @@ int yue_set_option(yue_ctx *c, const char *name, int64_t value) {
         return YUE_OK;
     }
     if (key.compare(0, 5, "wrmf_") == 0) return yue_host::wrmf_set_option(c, key, value);
+    if (key.compare(0, 4, "knn_") == 0) return yue_host::knn_set_option(c, key, value);
     return fail(YUE_ERR_ARG, "yue_set_option: unknown option " + key);
 }
 

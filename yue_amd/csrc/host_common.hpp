@@ -3,7 +3,7 @@
 //   core_host.hip   context, factors, interactions            bpr_host.hip   replay levels, S-rounds, epochs, CUNE, Adam, options
 //   chain_host.hip  exact sequential semantics as dataflow    scan_host.hip  predict + evalRanking's selection
 //   fism_host.hip   FISM                                      comm.hip       RCCL
-//   wrmf_host.hip   WRMF (ALS half-sweeps)
+//   wrmf_host.hip   WRMF (ALS half-sweeps)                     knn_host.hip   UserKNN (neighbours, ranking)
 #pragma once
 #include "../../include/yue_hip.h"
 
@@ -19,6 +19,7 @@
 
 struct ncclComm;
 struct yue_wrmf;                                     // wrmf_host.hip: pairs, schedules, workspaces of the WRMF half-sweeps
+struct yue_knn;                                      // knn_host.hip: pair lists, neighbour lists, ranking buffers of UserKNN
 
 namespace yue_host {
 
@@ -183,6 +184,7 @@ struct yue_ctx {
     int comm_version = 0, comm_nranks_reported = 0;
     hipEvent_t ev_scan0 = nullptr, ev_scan1 = nullptr;      // brackets of the scoring kernel (yue_get_scan_stats)
     yue_wrmf *wrmf = nullptr;            // WRMF state (yue_wrmf_set_pairs), owned by wrmf_host.hip
+    yue_knn *knn = nullptr;              // UserKNN state (yue_knn_set_pairs), owned by knn_host.hip
 };
 
 namespace yue_host {
@@ -201,4 +203,8 @@ int chain_stream(yue_ctx *c, int64_t T, double lr, double regU, double regI);
 void wrmf_release(yue_ctx *c);
 int wrmf_set_option(yue_ctx *c, const std::string &key, int64_t value);
 int wrmf_get_option(yue_ctx *c, const std::string &key, int64_t *value);
+// knn_host.hip: frees the UserKNN state; options "knn_*"
+void knn_release(yue_ctx *c);
+int knn_set_option(yue_ctx *c, const std::string &key, int64_t value);
+int knn_get_option(yue_ctx *c, const std::string &key, int64_t *value);
 }  // namespace yue_host

@@ -1,0 +1,258 @@
+// libyue_hip.so -- UserKNN (recommender/cf/UserKNN.py): exact top-K user neighbours and neighbourhood ranking (include/yue_hip.h).
+// Kernels: knn_kernels.hpp.  Needs no factors: the state is the pair lists of yue_knn_set_pairs and the neighbour lists.
+#include "host_common.hpp"
+
+#include "knn_kernels.hpp"
+
+#include <numeric>
+
+using yue_host::fail;
+
+struct yue_knn {
+    int64_t m = 0, n = 0, nnz = 0;
+    DevBuf<int64_t> u_ptr, i_ptr, cursor;
+    DevBuf<int32_t> u_items, u_counts, i_users;
+    int K = 0;                               // 0: no neighbour lists yet
+    DevBuf<int32_t> nbr, inter, uni;
+    DevBuf<int32_t> users, ids, len;
+    DevBuf<double> scores;
+    DevBuf<int> chunked;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    int64_t last_ns = 0, last_chunked = 0;
+    int range = yue::kKnnRange;              // options knn_range / knn_gather (tests lower them to reach the multi-pass paths)
+    int gather = yue::kKnnGather;
+};
+
+namespace yue_host {
+
+void knn_release(yue_ctx *c) {
+    yue_knn *k = c->knn;
+    if (!k) return;
+    k->u_ptr.release(); k->i_ptr.release(); k->cursor.release(); k->u_items.release(); k->u_counts.release(); k->i_users.release();
+    k->nbr.release(); k->inter.release(); k->uni.release(); k->users.release(); k->ids.release(); k->len.release();
+    k->scores.release(); k->chunked.release();
+    for (auto &e : k->ev) if (e) (void)hipEventDestroy(e);
+    delete k;
+    c->knn = nullptr;
+}
+
+}  // namespace yue_host
+
+namespace {
+
+int knn_state(yue_ctx *c, yue_knn **out) {
+    if (!c->knn) {
+        HIPCHK(hipSetDevice(c->device));
+        yue_knn *k = new yue_knn();
+        c->knn = k;
+        for (auto &e : k->ev) HIPCHK(hipEventCreate(&e));
+    }
+    *out = c->knn;
+    return YUE_OK;
+}
+
+// one direction's CSR: ptr[rows+1] from 0 to nnz, ids sorted-unique in [0, ids_bound), counts (when given) >= 1
+int check_csr(const int64_t *ptr, const int32_t *ids, const int32_t *cnt, int64_t rows, int64_t ids_bound, int64_t nnz, const char *what) {
+    const std::string at = std::string("yue_knn_set_pairs: ") + what;
+    if (!ptr || (nnz > 0 && !ids)) return fail(YUE_ERR_ARG, at + ": null array");
+    if (ptr[0] != 0 || ptr[rows] != nnz) return fail(YUE_ERR_ARG, at + " pointer must run from 0 to nnz");
+    for (int64_t r = 0; r < rows; ++r) {
+        if (ptr[r + 1] < ptr[r]) return fail(YUE_ERR_ARG, at + " pointer must be non-decreasing");
+        for (int64_t e = ptr[r]; e < ptr[r + 1]; ++e) {
+            if (ids[e] < 0 || ids[e] >= ids_bound) return fail(YUE_ERR_ARG, at + " id out of range");
+            if (e > ptr[r] && ids[e] <= ids[e - 1]) return fail(YUE_ERR_ARG, at + " rows must be sorted and unique");
+            if (cnt && cnt[e] < 1) return fail(YUE_ERR_ARG, at + " counts must be >= 1");
+        }
+    }
+    return YUE_OK;
+}
+
+template <typename T>
+int upload(DevBuf<T> &buf, const T *src, int64_t count) {
+    HIPCHK(buf.resize((size_t)std::max<int64_t>(count, 1)));
+    if (count > 0) HIPCHK(hipMemcpy(buf.p, src, (size_t)count * sizeof(T), hipMemcpyHostToDevice));
+    return YUE_OK;
+}
+
+yue::KnnArgs base_args(const yue_knn *k) {
+    yue::KnnArgs a{};
+    a.m = k->m; a.n = k->n;
+    a.u_ptr = k->u_ptr.p; a.u_items = k->u_items.p; a.u_counts = k->u_counts.p;
+    a.i_ptr = k->i_ptr.p; a.i_users = k->i_users.p;
+    a.K = k->K; a.range = k->range; a.gather = k->gather;
+    a.nbr = k->nbr.p; a.inter = k->inter.p; a.uni = k->uni.p;
+    return a;
+}
+
+int ready(yue_ctx *c, const char *who, yue_knn **out) {
+    if (!c) return fail(YUE_ERR_ARG, std::string(who) + ": null context");
+    if (!c->knn || c->knn->m == 0) return fail(YUE_ERR_ARG, std::string(who) + ": call yue_knn_set_pairs first");
+    if (c->knn->K == 0) return fail(YUE_ERR_ARG, std::string(who) + ": call yue_knn_neighbors first");
+    *out = c->knn;
+    return YUE_OK;
+}
+
+}  // namespace
+
+namespace yue_host {
+
+int knn_set_option(yue_ctx *c, const std::string &key, int64_t value) {
+    yue_knn *k = nullptr;
+    if (key == "knn_range") {
+        if (value < 64 || value > yue::kKnnRange) return fail(YUE_ERR_ARG, "yue_set_option: knn_range must be 64..4096");
+        int rc = knn_state(c, &k);
+        if (rc) return rc;
+        k->range = (int)value;
+        return YUE_OK;
+    }
+    if (key == "knn_gather") {
+        if (value < yue::kKnnMaxK || value > yue::kKnnGather) return fail(YUE_ERR_ARG, "yue_set_option: knn_gather must be 256..2048");
+        int rc = knn_state(c, &k);
+        if (rc) return rc;
+        k->gather = (int)value;
+        return YUE_OK;
+    }
+    return fail(YUE_ERR_ARG, "yue_set_option: unknown option " + key);
+}
+
+int knn_get_option(yue_ctx *c, const std::string &key, int64_t *value) {
+    const yue_knn *k = c->knn;
+    if (key == "knn_range") *value = k ? k->range : yue::kKnnRange;
+    else if (key == "knn_gather") *value = k ? k->gather : yue::kKnnGather;
+    else if (key == "knn_last_ns") *value = k ? k->last_ns : 0;                     // device time of the last neighbours / topn / predict call
+    else if (key == "knn_last_chunked_users") *value = k ? k->last_chunked : 0;     // users of the last topn scored in item-range chunks
+    else return fail(YUE_ERR_ARG, "yue_get_option: unknown option " + key);
+    return YUE_OK;
+}
+
+}  // namespace yue_host
+
+extern "C" {
+
+int yue_knn_set_pairs(yue_ctx *c, int64_t m, int64_t n, const int64_t *u_ptr, const int32_t *u_items, const int32_t *u_counts,
+                      const int64_t *i_ptr, const int32_t *i_users, int64_t nnz) {
+    if (!c) return fail(YUE_ERR_ARG, "yue_knn_set_pairs: null context");
+    if (m < 1 || n < 1 || nnz < 0) return fail(YUE_ERR_ARG, "yue_knn_set_pairs: need m >= 1, n >= 1, nnz >= 0");
+    if (m >= INT32_MAX || n >= ((int64_t)1 << 26))
+        return fail(YUE_ERR_ARG, "yue_knn_set_pairs: m must be below 2^31 - 1 and n below 2^26 (similarities are compared as exact integer ratios)");
+    if (nnz > 0 && !u_counts) return fail(YUE_ERR_ARG, "yue_knn_set_pairs: null user-major counts");
+    int rc = check_csr(u_ptr, u_items, u_counts, m, n, nnz, "user-major");
+    if (!rc) rc = check_csr(i_ptr, i_users, nullptr, n, m, nnz, "item-major");
+    if (rc) return rc;
+    {   // the item-major lists must be the transpose of the user-major ones (users ascending: the cursors rely on it)
+        std::vector<int64_t> at(i_ptr, i_ptr + n);
+        for (int64_t u = 0; u < m; ++u)
+            for (int64_t e = u_ptr[u]; e < u_ptr[u + 1]; ++e) {
+                const int32_t i = u_items[e];
+                const int64_t q = at[(size_t)i]++;
+                if (q >= i_ptr[i + 1] || i_users[q] != (int32_t)u)
+                    return fail(YUE_ERR_ARG, "yue_knn_set_pairs: the item-major pairs are not the transpose of the user-major pairs (item " + std::to_string(i) + ")");
+            }
+    }
+    HIPCHK(hipSetDevice(c->device));
+    yue_knn *k = nullptr;
+    if ((rc = knn_state(c, &k))) return rc;
+    k->m = 0; k->K = 0;                                          // invalid until everything is up
+    if ((rc = upload(k->u_ptr, u_ptr, m + 1)) || (rc = upload(k->u_items, u_items, nnz)) || (rc = upload(k->u_counts, u_counts, nnz)) ||
+        (rc = upload(k->i_ptr, i_ptr, n + 1)) || (rc = upload(k->i_users, i_users, nnz)))
+        return rc;
+    HIPCHK(k->cursor.resize((size_t)std::max<int64_t>(nnz, 1)));
+    HIPCHK(k->chunked.resize(1));
+    k->m = m; k->n = n; k->nnz = nnz;
+    return YUE_OK;
+}
+
+int yue_knn_neighbors(yue_ctx *c, int K, int32_t *nbr_out, int32_t *inter_out, int32_t *union_out) {
+    if (!c) return fail(YUE_ERR_ARG, "yue_knn_neighbors: null context");
+    yue_knn *k = c->knn;
+    if (!k || k->m == 0) return fail(YUE_ERR_ARG, "yue_knn_neighbors: call yue_knn_set_pairs first");
+    if (K < 1 || K > yue::kKnnMaxK) return fail(YUE_ERR_ARG, "yue_knn_neighbors: K = " + std::to_string(K) + " is not supported (1 <= K <= 256)");
+    HIPCHK(hipSetDevice(c->device));
+    const size_t cells = (size_t)k->m * (size_t)K;
+    HIPCHK(k->nbr.resize(cells)); HIPCHK(k->inter.resize(cells)); HIPCHK(k->uni.resize(cells));
+    k->K = K;
+    yue::KnnArgs a = base_args(k);
+    a.cursor = k->cursor.p;
+    HIPCHK(hipEventRecord(k->ev[0], c->stream));
+    hipLaunchKernelGGL(yue::k_knn_neighbors, dim3((unsigned)k->m), dim3(yue::kKnnThreads), 0, c->stream, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(k->ev[1], c->stream));
+    if (nbr_out) HIPCHK(hipMemcpyAsync(nbr_out, k->nbr.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (inter_out) HIPCHK(hipMemcpyAsync(inter_out, k->inter.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (union_out) HIPCHK(hipMemcpyAsync(union_out, k->uni.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    float ms = 0.0f;
+    HIPCHK(hipEventElapsedTime(&ms, k->ev[0], k->ev[1]));
+    k->last_ns = (int64_t)(1e6 * (double)ms);
+    return YUE_OK;
+}
+
+int yue_knn_topn(yue_ctx *c, const int32_t *users, int64_t nu, int N, int32_t *ids_out, double *scores_out, int32_t *len_out) {
+    yue_knn *k = nullptr;
+    int rc = ready(c, "yue_knn_topn", &k);
+    if (rc) return rc;
+    if (N < 1 || N > yue::kKnnMaxN) return fail(YUE_ERR_ARG, "yue_knn_topn: N = " + std::to_string(N) + " is not supported (1 <= N <= 100)");
+    if (nu < 0 || nu >= INT32_MAX || (nu > 0 && (!users || !ids_out || !scores_out || !len_out)))
+        return fail(YUE_ERR_ARG, "yue_knn_topn: need 0 <= nu < 2^31 - 1 and non-null arrays");
+    for (int64_t b = 0; b < nu; ++b)
+        if (users[b] < 0 || users[b] >= k->m) return fail(YUE_ERR_ARG, "yue_knn_topn: user id out of range");
+    if (nu == 0) return YUE_OK;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(k->users.resize((size_t)nu)); HIPCHK(k->ids.resize((size_t)nu * N)); HIPCHK(k->scores.resize((size_t)nu * N)); HIPCHK(k->len.resize((size_t)nu));
+    HIPCHK(hipMemcpyAsync(k->users.p, users, (size_t)nu * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemsetAsync(k->chunked.p, 0, sizeof(int), c->stream));
+    yue::KnnArgs a = base_args(k);
+    a.users = k->users.p; a.N = N; a.exclude_own = 1;
+    a.ids_out = k->ids.p; a.scores_out = k->scores.p; a.len_out = k->len.p; a.chunked_users = k->chunked.p;
+    HIPCHK(hipEventRecord(k->ev[0], c->stream));
+    hipLaunchKernelGGL(yue::k_knn_topn, dim3((unsigned)nu), dim3(yue::kKnnThreads), 0, c->stream, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(k->ev[1], c->stream));
+    int chunked = 0;
+    HIPCHK(hipMemcpyAsync(ids_out, k->ids.p, (size_t)nu * N * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(scores_out, k->scores.p, (size_t)nu * N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(len_out, k->len.p, (size_t)nu * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&chunked, k->chunked.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    float ms = 0.0f;
+    HIPCHK(hipEventElapsedTime(&ms, k->ev[0], k->ev[1]));
+    k->last_ns = (int64_t)(1e6 * (double)ms);
+    k->last_chunked = chunked;
+    return YUE_OK;
+}
+
+int yue_knn_predict(yue_ctx *c, int32_t user, int64_t cap, int32_t *items_out, double *scores_out, int64_t *len_out) {
+    yue_knn *k = nullptr;
+    int rc = ready(c, "yue_knn_predict", &k);
+    if (rc) return rc;
+    if (user < 0 || user >= k->m) return fail(YUE_ERR_ARG, "yue_knn_predict: user id out of range");
+    if (cap < 0 || (cap > 0 && (!items_out || !scores_out)) || !len_out) return fail(YUE_ERR_ARG, "yue_knn_predict: need cap >= 0 and non-null arrays");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(k->scores.resize((size_t)k->n));
+    yue::KnnArgs a = base_args(k);
+    a.user = user; a.item_scores = k->scores.p;
+    HIPCHK(hipEventRecord(k->ev[0], c->stream));
+    hipLaunchKernelGGL(yue::k_knn_predict_scores, dim3((unsigned)((k->n + yue::kKnnThreads - 1) / yue::kKnnThreads)), dim3(yue::kKnnThreads), 0, c->stream, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(k->ev[1], c->stream));
+    std::vector<double> sc((size_t)k->n);
+    HIPCHK(hipMemcpyAsync(sc.data(), k->scores.p, (size_t)k->n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    float ms = 0.0f;
+    HIPCHK(hipEventElapsedTime(&ms, k->ev[0], k->ev[1]));
+    k->last_ns = (int64_t)(1e6 * (double)ms);
+    // the one-user list: the scored items by (score descending, item ascending)
+    std::vector<int32_t> order;
+    for (int64_t i = 0; i < k->n; ++i)
+        if (sc[(size_t)i] >= 0.0) order.push_back((int32_t)i);
+    std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return sc[(size_t)x] > sc[(size_t)y]; });
+    const int64_t len = (int64_t)order.size();
+    for (int64_t r = 0; r < std::min(len, cap); ++r) {
+        items_out[r] = order[(size_t)r];
+        scores_out[r] = sc[(size_t)order[(size_t)r]];
+    }
+    *len_out = len;
+    return YUE_OK;
+}
+
+}  // extern "C"

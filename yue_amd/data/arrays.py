@@ -201,3 +201,16 @@ def ranking_measure_ids(test_indptr, test_indices, users, ids, top, item_count):
         out += ['Top ' + str(n) + '\n', 'Precision:' + str(prec) + '\n', 'Recall:' + str(rec) + '\n', 'F1:' + str(f1) + '\n',
                 'MAP:' + str(float(ap)) + '\n', 'Coverage:' + str(cov) + '\n']
     return out
+
+
+def ranking_measure_lists(test_indptr, test_indices, users, ids, lens, top, item_count):
+    """Measure.rankingMeasure on integer lists of different lengths: ``ids[nu, N]`` padded with -1 behind ``lens[nu]``
+    (the list-returning recommenders, e.g. UserKNN).  The padding is never an item: it counts neither in hits nor in
+    coverage.  Precision still divides by n for a short list, as the reference does.  Same sums in the same order as
+    the text path, so the strings equal those of the same lists given as names."""
+    from ..evaluation.measure import Measure
+    origin, res = {}, {}
+    for row, u in enumerate(np.asarray(users, np.int64)):
+        origin[int(u)] = set(int(i) for i in test_indices[test_indptr[u]:test_indptr[u + 1]])
+        res[int(u)] = [int(i) for i in ids[row, :lens[row]]]
+    return Measure.rankingMeasure(origin, res, top, item_count)
