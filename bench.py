@@ -14,8 +14,12 @@ For N > 1 the default workload is one GPU's share of BASELINE config 4 per rank 
 line carries `comm` (all-reduce bytes and collectives per epoch and rank, the time the compute stream waited for the
 collective stream, RCCL version and rank count).
 
-One JSON line on rank 0, with `roofline` (dominant kernel, HIP events on the library's stream),
-`cpu_baseline` (oracle/ timed on one host core, N=1 only) and, at N=1:
+One JSON line on rank 0, with `roofline` (dominant kernel, HIP events on the library's stream around the timed epochs).
+A plain run does only that: set-up, warm-up, the timed steps, --dump-outputs, the line.  Whatever takes runs of its own
+comes with `--full` (off by default; `--no-cpu-baseline` / `--no-secondary` leave parts of it out):
+  `cpu_baseline`  oracle/ timed on one host core (N=1 only; the scoring and FISM lines have their own);
+  FISM only: `config.sequential_device_pass_draws_per_s`, the sequential device pass on the first users;
+and at N=1 on the default workload:
   `config.deviation_vs_sequential`  how far ONE epoch of the timed S-round semantics lands from the reference's sequential
                   loop run on the same factors and negatives (the exact device path, itself checked against the oracle);
   `secondary.exact`  the EXACT path (recommender/cf/BPR.py:40-62 semantics, chain_kernels.hpp) on config 3, config 2 and one rank's share of config 4:
@@ -445,7 +449,7 @@ def bench_scoring(args, cp):
         sel = dump_rows(len(users), N * (ids.itemsize * 2 + sc.itemsize))
         dump_outputs(args.dump_outputs, {'user_index': users[sel], 'topn_ids': ids[sel], 'topn_scores': sc[sel]})
     cpu = None
-    if cp.rank == 0 and cp.world == 1 and not args.no_cpu_baseline:
+    if cp.rank == 0 and cp.world == 1 and args.full and not args.no_cpu_baseline:
         cpu = scoring_cpu_baseline(dev, data, users, ids, N, n, 12.0)
     if cp.rank == 0:
         done, total = dev.scan_work()
@@ -514,16 +518,18 @@ def bench_fism(args, cp):
         dump_outputs(args.dump_outputs, {'fism_sums': np.array(sums, np.float64), 'item_index': rows,
                                          'P_rows': Pm[rows], 'Q_rows': Qm[rows], 'Bi_rows': Bm[rows]})
         del Pm, Qm, Bm
-    # the sequential device pass and the NumPy loop on the first users of the same problem
+    # --full: the sequential device pass and the NumPy loop on the first users of the same problem
     su = min(m, 2000)
     sl = slice(0, int(ptr[su]))
     nsl = slice(0, int(np.diff(ptr[:su + 1])[np.diff(ptr[:su + 1]) > 1].sum()) * rho)
-    dev.fism_set_model(P0, Q0, B0)
-    t1 = time.perf_counter()
-    dev.fism_epoch(ptr[:su + 1], ev_i[sl], negs[0][nsl], rho, coef[:su], lr, reg, reg)
-    seq_dt = time.perf_counter() - t1
+    seq = {}
+    if args.full:
+        dev.fism_set_model(P0, Q0, B0)
+        t1 = time.perf_counter()
+        dev.fism_epoch(ptr[:su + 1], ev_i[sl], negs[0][nsl], rho, coef[:su], lr, reg, reg)
+        seq['sequential_device_pass_draws_per_s'] = (nsl.stop - nsl.start) / (time.perf_counter() - t1)
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         from oracle.numpy_fism import fism_epoch
         P, Q, Bi = P0.copy(), Q0.copy(), B0.copy()
         t1 = time.perf_counter()
@@ -539,8 +545,7 @@ def bench_fism(args, cp):
         'dtype': 'f64 (P, Bi) / f32 (Q)', 'data': 'synthetic',
         'config': {'workload': 'FISM: %d users x %d items, %d events/user, k=%d, rho=%d, alpha=%g, lr=%g, reg=%g, rounds of %d users; host work of a call '
                                '(upload of events and negatives) included in value' % (m, n, d, k, rho, alpha, lr, reg, round_users),
-                   'final_half_sq_error': half,
-                   'sequential_device_pass_draws_per_s': (nsl.stop - nsl.start) / seq_dt},
+                   'final_half_sq_error': half, **seq},
         'roofline': {'bound': 'hbm', 'kernel': 'k_fism_round_lds<KR=%d> (one wave per user, working and round-start rows in LDS, rows of one user stored in place: the user\'s chain of draws, then the contended atomics of the shared rows)' % (1 if k <= 64 else 2 if k <= 128 else 4),
                      'achieved': ach / 1e9, 'peak': HBM_PEAK / 1e9, 'unit': 'GB/s', 'frac': ach / HBM_PEAK, 'algorithmic_bytes_per_draw': bytes_per_draw, 'traffic': None},
         'cpu_baseline': cpu}))
@@ -555,8 +560,11 @@ def main():
     ap.add_argument('--warmup', type=int, default=1)
     ap.add_argument('--workload', default=None, choices=sorted(WORKLOADS), help='default: c3 on one GPU, c4shard per rank on several')
     ap.add_argument('--round-events', type=int, default=0, help='events per S-round; 0 = the library\'s default for this device and problem (yue_default_round_events)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-secondary', action='store_true', help='skip the scoring line (secondary.c5) of the default run')
+    ap.add_argument('--full', action='store_true',
+                    help='after the line\'s own measurement also run what takes runs of its own: CPU baselines, the FISM sequential pass, '
+                         'and on the default one-GPU workload the deviation from the sequential loop and the secondary lines (exact path, scoring)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baselines')
+    ap.add_argument('--no-secondary', action='store_true', help='with --full: skip the deviation and the secondary lines of the default workload')
     ap.add_argument('--scan-f32', action='store_true', help='scoring workloads: force the exact f32-MFMA kernel')
     ap.add_argument('--tpw', type=int, default=0, help='tuning: events per wave in the round kernel (0 = default)')
     ap.add_argument('--opt', action='append', default=[], metavar='NAME=VALUE', help='tuning: yue_set_option(NAME, VALUE), repeatable')
@@ -663,11 +671,11 @@ def main():
                                    % (args.workload.upper(), k, m, n, d, E, args.round_events, LR, REG_U),
                        'semantics': ('S-round with sequential user rows (DESIGN.md section 3): a wave owns a user and applies the user\'s triplets in the reference\'s order '
                                      'with P[u] in registers; item rows are read as the round of W events started, their differences summed per row and added once per round. '
-                                     'NOT the reference\'s strictly sequential loop: config.deviation_vs_sequential says how far one epoch lands from it; '
-                                     'secondary.exact is the path with the reference\'s semantics')
+                                     'NOT the reference\'s strictly sequential loop: config.deviation_vs_sequential (--full) says how far one epoch lands from it; '
+                                     'secondary.exact (--full) is the path with the reference\'s semantics')
                                     if dev.get_option('round_last_user_seq') else
                                     ('S-round (DESIGN.md section 3): every triplet of a round of W events is evaluated on the factors as the round started, per-row differences '
-                                     'summed and added once; NOT the reference\'s strictly sequential loop (secondary.exact)'),
+                                     'summed and added once; NOT the reference\'s strictly sequential loop (secondary.exact, --full)'),
                        'round_events': args.round_events, 'parallelism': 'items sharded x%d, users replicated' % world,
                        'setup_s': round(setup_s, 1), 'final_nll_per_triplet': nll / E},
             'roofline': {'bound': 'hbm', 'kernel': round_kernel_label(dev, k),
@@ -690,10 +698,10 @@ def main():
                            'compute_stream_wait_ms_last_epoch': comm['wait_ms'], 'nranks_rccl': comm['nranks'], 'rccl_version': comm['rccl_version'],
                            'what': 'ncclAllReduce (fp32 sum, in place) of the user-factor differences of a group of user blocks, on a second HIP stream beside the next '
                                    'group\'s rounds; wait = end of the last group\'s all-reduce + apply minus end of the last round launch (HIP events)'}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             j0 = dev.sample_negatives(seed, 0)
             out['cpu_baseline'] = cpu_baseline(data, P0, Q0, j0, k)
-        if world == 1 and not args.no_secondary and not args.force_comm and args.workload == 'c3':
+        if world == 1 and args.full and not args.no_secondary and not args.force_comm and args.workload == 'c3':
             out['secondary'] = {'c5': secondary_scoring(dev, data, m, n, k, args.no_cpu_baseline,
                                                         'as the %d S-round epochs of this run (warm-up + timed) left them' % (args.warmup + args.steps))}
             dev_out, _ = deviation_vs_sequential(dev, P0, Q0, seed, args.round_events, E)

@@ -4,9 +4,9 @@ tag=${1:-r04_f}; out=gpurun_out/$tag; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 timeout -k 10 600 python -m pytest tests/test_gpu_fism.py -q -m gpu > $out/fism_tests.log 2>&1; echo "pytest rc=$?" >> $out/fism_tests.log; tail -3 $out/fism_tests.log
 grep -q "rc=0" $out/fism_tests.log || exit 1
-timeout -k 10 300 python bench.py --workload fism --steps 3 --warmup 1 > $out/bench_fism.json 2> $out/bench_fism.err && echo fism ok
-timeout -k 10 300 python bench.py --workload fism --steps 3 --warmup 1 --no-cpu-baseline --opt fism_inplace=0 > $out/bench_fism_inplace0.json 2> $out/bench_fism_inplace0.err && echo fism inplace0 ok
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/kf -- python3 bench.py --workload fism --steps 2 --warmup 1 --no-cpu-baseline > $out/kf.log 2>&1 && cp $(find $out/kf -name '*kernel_stats.csv' | head -1) $out/fism_kernel_stats.csv && rm -rf $out/kf && echo fism kernel stats ok
+timeout -k 10 300 python bench.py --full --workload fism --steps 3 --warmup 1 > $out/bench_fism.json 2> $out/bench_fism.err && echo fism ok
+timeout -k 10 300 python bench.py --full --workload fism --steps 3 --warmup 1 --no-cpu-baseline --opt fism_inplace=0 > $out/bench_fism_inplace0.json 2> $out/bench_fism_inplace0.err && echo fism inplace0 ok
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/kf -- python3 bench.py --full --workload fism --steps 2 --warmup 1 --no-cpu-baseline > $out/kf.log 2>&1 && cp $(find $out/kf -name '*kernel_stats.csv' | head -1) $out/fism_kernel_stats.csv && rm -rf $out/kf && echo fism kernel stats ok
 python - $tag <<'PY'
 import json
 for f in ('bench_fism', 'bench_fism_inplace0'):
