@@ -307,6 +307,32 @@ int yue_knn_neighbors(yue_ctx *ctx, int K, int32_t *nbr_out, int32_t *inter_out,
 int yue_knn_predict(yue_ctx *ctx, int32_t user, int64_t cap, int32_t *items_out, double *scores_out, int64_t *len_out);
 int yue_knn_topn(yue_ctx *ctx, const int32_t *users, int64_t nu, int N, int32_t *ids_out, double *scores_out, int32_t *len_out);
 
+/*
+ * IPF (reference recommender/cf/IPF.py) -- ranking by four typed 3-hop paths over the session temporal graph.  Needs no
+ * factors.  UL[u] is u's training events in order (duplicates kept), S[u] = UL[u][-10:] its session.
+ *   yue_ipf_set_graph  the graph and its weights, computed by the caller as the reference writes them:
+ *                    u_ptr[m+1] / u_items   each user's distinct items of UL[u] in first-occurrence order (< 2^18 per user)
+ *                    s_ptr[m+1] / s_items   each user's distinct items of S[u] in first-occurrence order
+ *                    hu_ptr[n+1] / hu_users item -> its distinct users in listened (insertion) order; pos = index in the row
+ *                    hs_ptr[n+1] / hs_users / hs_pos  item -> the distinct users whose session holds it, in user order, with
+ *                                           each one's first position in the list that keeps duplicates (< 2^26)
+ *                    w_user[m] = 1/L^rho, w_sess[m] = 1/min(10, L)^rho, p_i2u[n] = (eta/(eta nU + nS))^rho,
+ *                    p_i2s[n] = (1/(eta nU + nS))^rho; r_user = beta, r_sess = 1 - beta.  Needs m, n < 2^26.
+ *   yue_ipf_predict    the full list of one user: every item some path reaches, score = the fp64 sum over the paths in order,
+ *                    ordered by (score descending, first insertion ascending), the user's own items included.  Writes
+ *                    min(len, cap) entries; *len_out = the full length.
+ *   yue_ipf_topn       the same lists for `users` without each user's own training items, cut at N (1 <= N <= 100): ids_out /
+ *                    scores_out [nu][N] padded with -1 / 0, len_out[nu] the real lengths (a list may be shorter than N).
+ * Options: "ipf_slots" (1..4096, queries in flight per launch, default 1024, capped so that the work arrays stay within
+ * 4 GiB); read-only "ipf_last_ns" (device time of the last predict / topn launch).
+ */
+int yue_ipf_set_graph(yue_ctx *ctx, int64_t m, int64_t n, const int64_t *u_ptr, const int32_t *u_items, const int64_t *s_ptr,
+                      const int32_t *s_items, const int64_t *hu_ptr, const int32_t *hu_users, const int64_t *hs_ptr,
+                      const int32_t *hs_users, const int32_t *hs_pos, const double *w_user, const double *w_sess,
+                      const double *p_i2u, const double *p_i2s, double r_user, double r_sess);
+int yue_ipf_predict(yue_ctx *ctx, int32_t user, int64_t cap, int32_t *items_out, double *scores_out, int64_t *len_out);
+int yue_ipf_topn(yue_ctx *ctx, const int32_t *users, int64_t nu, int N, int32_t *ids_out, double *scores_out, int32_t *len_out);
+
 /* Multi-GPU (one process per GPU, RCCL over xGMI).  Rank 0 creates the id, the caller ships
  * the 128 bytes to the other ranks (any side channel), every rank calls yue_comm_init. */
 int yue_comm_unique_id(void *id128_out);

@@ -26,7 +26,8 @@ SYMBOLS = ['yue_last_error', 'yue_version', 'yue_ctx_create', 'yue_ctx_destroy',
            'yue_default_round_events', 'yue_epoch_plan',
            'yue_fism_set_model', 'yue_fism_get_model', 'yue_fism_epoch', 'yue_fism_rounds', 'yue_fism_scores', 'yue_fism_topn_scan',
            'yue_wrmf_set_pairs', 'yue_wrmf_half_sweep',
-           'yue_knn_set_pairs', 'yue_knn_neighbors', 'yue_knn_predict', 'yue_knn_topn']
+           'yue_knn_set_pairs', 'yue_knn_neighbors', 'yue_knn_predict', 'yue_knn_topn',
+           'yue_ipf_set_graph', 'yue_ipf_predict', 'yue_ipf_topn']
 
 
 class YueHipError(RuntimeError):
@@ -101,6 +102,7 @@ class Device(object):
         self._ctx = C.c_void_p()
         self.m = self.n = self.k = self.E = 0
         self.knn_m = self.knn_n = 0
+        self.ipf_m = self.ipf_n = 0
         self._chk(self._lib.yue_ctx_create(C.c_int(device), C.byref(self._ctx)))
 
     # reference convention: print, exit(-1)
@@ -396,6 +398,54 @@ class Device(object):
         scores = np.empty((nu, max(int(N), 0)), np.float64)
         lens = np.empty(nu, np.int32)
         self._chk(self._lib.yue_knn_topn(self._ctx, up, C.c_int64(nu), C.c_int(N), ids.ctypes.data_as(C.POINTER(C.c_int32)),
+                                         scores.ctypes.data_as(C.POINTER(C.c_double)), lens.ctypes.data_as(C.POINTER(C.c_int32))))
+        return ids, scores, lens
+
+    # -- IPF (needs no factors) -----------------------------------------------------------------
+    def ipf_set_graph(self, g):
+        """Upload the session temporal graph ``g`` (yue_amd/recommender/cf/IPF.py: ipf_graph): per-user distinct lists
+        u_ptr/u_items and s_ptr/s_items, holder lists hu_ptr/hu_users and hs_ptr/hs_users/hs_pos, the weights w_user,
+        w_sess, p_i2u, p_i2s and r_user = beta, r_sess = 1 - beta."""
+        m, n = int(g['m']), int(g['n'])
+        keep = []
+
+        def arr(key, conv, size=None):
+            a, p = conv(g[key] if len(g[key]) else np.zeros(1, np.int32))
+            assert size is None or len(a) == size, 'ipf_set_graph: %s must hold %d entries' % (key, size)
+            keep.append(a)
+            return p
+        ptrs = [arr('u_ptr', _i64, m + 1), arr('u_items', _i32), arr('s_ptr', _i64, m + 1), arr('s_items', _i32),
+                arr('hu_ptr', _i64, n + 1), arr('hu_users', _i32), arr('hs_ptr', _i64, n + 1), arr('hs_users', _i32),
+                arr('hs_pos', _i32)]
+        assert len(g['u_items']) == g['u_ptr'][-1] and len(g['s_items']) == g['s_ptr'][-1] and len(g['hu_users']) == g['hu_ptr'][-1] \
+            and len(g['hs_users']) == g['hs_ptr'][-1] == len(g['hs_pos']), 'ipf_set_graph: list lengths must match their pointers'
+        weights = []
+        for key, size in (('w_user', m), ('w_sess', m), ('p_i2u', n), ('p_i2s', n)):
+            a, p = _f64(g[key])
+            assert len(a) == size, 'ipf_set_graph: %s must hold %d entries' % (key, size)
+            keep.append(a)
+            weights.append(p)
+        self._chk(self._lib.yue_ipf_set_graph(self._ctx, C.c_int64(m), C.c_int64(n), *ptrs, *weights,
+                                              C.c_double(g['r_user']), C.c_double(g['r_sess'])))
+        self.ipf_m, self.ipf_n = m, n
+
+    def ipf_predict(self, user):
+        """(items int32, scores float64): the full list of one user by (score desc, first insertion asc), own items included."""
+        items = np.empty(max(self.ipf_n, 1), np.int32)
+        scores = np.empty(max(self.ipf_n, 1), np.float64)
+        length = C.c_int64()
+        self._chk(self._lib.yue_ipf_predict(self._ctx, C.c_int32(int(user)), C.c_int64(self.ipf_n), items.ctypes.data_as(C.POINTER(C.c_int32)),
+                                            scores.ctypes.data_as(C.POINTER(C.c_double)), C.byref(length)))
+        return items[:length.value], scores[:length.value]
+
+    def ipf_topn(self, users, N):
+        """(ids int32 [nu, N] -1 padded, scores float64 [nu, N] 0 padded, lens int32 [nu]) without each user's own items."""
+        users, up = _i32(users)
+        nu = len(users)
+        ids = np.empty((nu, max(int(N), 0)), np.int32)
+        scores = np.empty((nu, max(int(N), 0)), np.float64)
+        lens = np.empty(nu, np.int32)
+        self._chk(self._lib.yue_ipf_topn(self._ctx, up, C.c_int64(nu), C.c_int(N), ids.ctypes.data_as(C.POINTER(C.c_int32)),
                                          scores.ctypes.data_as(C.POINTER(C.c_double)), lens.ctypes.data_as(C.POINTER(C.c_int32))))
         return ids, scores, lens
 

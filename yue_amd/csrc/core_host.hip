@@ -74,6 +74,7 @@ int yue_ctx_destroy(yue_ctx *c) {
     c->ch_run_u.release(); c->ch_tmp.release(); c->ch_Qv.release(); c->ch_Pv.release(); c->ch_ctl.release(); c->ch_stats.release();
     yue_host::wrmf_release(c);
     yue_host::knn_release(c);
+    yue_host::ipf_release(c);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return YUE_OK;

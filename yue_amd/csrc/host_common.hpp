@@ -4,6 +4,7 @@
 //   chain_host.hip  exact sequential semantics as dataflow    scan_host.hip  predict + evalRanking's selection
 //   fism_host.hip   FISM                                      comm.hip       RCCL
 //   wrmf_host.hip   WRMF (ALS half-sweeps)                     knn_host.hip   UserKNN (neighbours, ranking)
+//   ipf_host.hip    IPF (session-graph ranking)
 #pragma once
 #include "../../include/yue_hip.h"
 
@@ -20,6 +21,7 @@
 struct ncclComm;
 struct yue_wrmf;                                     // wrmf_host.hip: pairs, schedules, workspaces of the WRMF half-sweeps
 struct yue_knn;                                      // knn_host.hip: pair lists, neighbour lists, ranking buffers of UserKNN
+struct yue_ipf;                                      // ipf_host.hip: session temporal graph, weights, per-slot work arrays of IPF
 
 namespace yue_host {
 
@@ -185,6 +187,7 @@ struct yue_ctx {
     hipEvent_t ev_scan0 = nullptr, ev_scan1 = nullptr;      // brackets of the scoring kernel (yue_get_scan_stats)
     yue_wrmf *wrmf = nullptr;            // WRMF state (yue_wrmf_set_pairs), owned by wrmf_host.hip
     yue_knn *knn = nullptr;              // UserKNN state (yue_knn_set_pairs), owned by knn_host.hip
+    yue_ipf *ipf = nullptr;              // IPF state (yue_ipf_set_graph), owned by ipf_host.hip
 };
 
 namespace yue_host {
@@ -207,4 +210,8 @@ int wrmf_get_option(yue_ctx *c, const std::string &key, int64_t *value);
 void knn_release(yue_ctx *c);
 int knn_set_option(yue_ctx *c, const std::string &key, int64_t value);
 int knn_get_option(yue_ctx *c, const std::string &key, int64_t *value);
+// ipf_host.hip: frees the IPF state; options "ipf_*"
+void ipf_release(yue_ctx *c);
+int ipf_set_option(yue_ctx *c, const std::string &key, int64_t value);
+int ipf_get_option(yue_ctx *c, const std::string &key, int64_t *value);
 }  // namespace yue_host

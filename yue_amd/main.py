@@ -4,7 +4,7 @@ import time
 from .tool.config import Config
 from .yue import Yue
 
-MENU = {'1': 'BPR', '2': 'FISM', '3': 'WRMF', '5': 'UserKNN', 'a1': 'CUNE'}
+MENU = {'1': 'BPR', '2': 'FISM', '3': 'WRMF', '4': 'IPF', '5': 'UserKNN', 'a1': 'CUNE'}
 
 
 def main():
@@ -12,7 +12,7 @@ def main():
     print('   Yue: Library for Music Recommendation (MI355X BPR path).   ')
     print('=' * 80)
     print('CF-based Recommenders:')
-    print('1. BPR   2. FISM   3. WRMF   5. UserKNN')
+    print('1. BPR   2. FISM   3. WRMF   4. IPF   5. UserKNN')
     print('Advanced Recommenders:')
     print('a1. CUNE (training loop; needs -friends, see recommender/advanced/CUNE.py)')
     print('=' * 80)
