@@ -126,6 +126,7 @@ def test_config4_shard_exact_epoch_matches_the_sequential_oracle(orc):
     print('C4 shard exact epoch on the device (%.0f ms incl. first-call allocations) vs the sequential oracle: bit-equal P %.5f Q %.5f, rel P %.1e Q %.1e'
           % (1e3 * t_dev, np.mean(Px == P0), np.mean(Qx == Q0), rel_err(Px, P0), rel_err(Qx, Q0)))
     assert rel_err(Px, P0) < 1e-6 and rel_err(Qx, Q0) < 1e-6 and abs(nll_x - nll_s) <= 1e-9 * nll_s
+    assert np.array_equal(Px, P0) and np.array_equal(Qx, Q0)
     print('C4 shard, single-precision coefficient (dataflow launch %.0f ms): bit-equal P %.5f Q %.5f, rel P %.1e Q %.1e, loss rel %.1e'
           % (1e-3 * us_f, np.mean(Pf == P0), np.mean(Qf == Q0), rel_err(Pf, P0), rel_err(Qf, Q0), abs(nll_f - nll_s) / nll_s))
     assert rel_err(Pf, P0) < 1e-5 and rel_err(Qf, Q0) < 1e-5 and abs(nll_f - nll_s) <= 1e-6 * nll_s
@@ -166,9 +167,10 @@ def _round_semantics_vs_sequential(orc, m, n, d, k, tag):
         dev.close()
     Ps, Qs = P0.copy(), Q0.copy()
     nll_s = orc.bpr_sequential(Ps, Qs, ev_u, data['ev_i'], j, LR, REG_U, REG_I)
-    assert rel_err(Px, Ps) < 1e-6 and rel_err(Qx, Qs) < 1e-6 and abs(nll_x - nll_s) <= 1e-9 * nll_s
     print('%s exact epoch on the device (dataflow launch %.0f ms) vs the sequential oracle: bit-equal P %.5f Q %.5f, rel P %.1e Q %.1e'
           % (tag, 1e-3 * us_x, np.mean(Px == Ps), np.mean(Qx == Qs), rel_err(Px, Ps), rel_err(Qx, Qs)))
+    assert rel_err(Px, Ps) < 1e-6 and rel_err(Qx, Qs) < 1e-6 and abs(nll_x - nll_s) <= 1e-9 * nll_s
+    assert np.array_equal(Px, Ps) and np.array_equal(Qx, Qs)
     for xcd, (nll_f, us_f, Pf, Qf) in enumerate(fast):
         print('%s, single-precision coefficient%s (dataflow launch %.0f ms = %.3e triplets/s): bit-equal P %.5f Q %.5f, rel P %.1e Q %.1e, loss rel %.1e'
               % (tag, ', one XCD' if xcd else '', 1e-3 * us_f, E / (1e-6 * us_f), np.mean(Pf == Ps), np.mean(Qf == Qs), rel_err(Pf, Ps), rel_err(Qf, Qs), abs(nll_f - nll_s) / nll_s))

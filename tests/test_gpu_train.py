@@ -104,6 +104,7 @@ def test_replay_edge_cases(dev, orc):
     nll_o = orc.bpr_sequential(Po, Qo, u, i, j, 0.05, 0.02, 0.03)
     P, Q = dev.get_factors()
     assert rel_err(P, Po) < 1e-6 and rel_err(Q, Qo) < 1e-6 and abs(nll - nll_o) < 1e-9 * nll_o
+    assert np.array_equal(P, Po) and np.array_equal(Q, Qo)
     # empty stream is a no-op
     assert dev.bpr_replay(u[:0], i[:0], j[:0], 0.05, 0.02, 0.03) == 0.0
     P2, Q2 = dev.get_factors()

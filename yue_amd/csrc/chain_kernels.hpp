@@ -487,6 +487,7 @@ struct TrioBox {
     unsigned long long cw[kTrioRing][64];         // from wave C: {coefficient of the slot's triplet (low), sequence number it answers (high)}
     unsigned sdone[2][64];                 // from the two S waves: last packet each is done with (a slot is reused kTrioRing packets later)
     unsigned runbox[kTrioRing][64];        // from wave L0 to wave L1: the runs it has claimed (lanes 0..4: first event lo / hi, length, number of the start packet, run counter)
+    unsigned runtaken[64];                 // from wave L1 to wave L0: the last run counter L1 has read from the mailbox
 };
 static_assert(sizeof(TrioBox<4>) <= 64 * 1024, "static LDS");
 
@@ -533,6 +534,7 @@ __global__ void __launch_bounds__(320) k_bpr_chain3(ChainArgs a, const int32_t *
     }
     for (int t = threadIdx.x; t < kTrioRing * 64; t += 320) { box.hdr[t >> 6][t & 63] = 0ull; box.cw[t >> 6][t & 63] = 0ull; box.runbox[t >> 6][t & 63] = 0u; }
     if (threadIdx.x < 128) box.sdone[threadIdx.x >> 6][threadIdx.x & 63] = 0u;
+    if (threadIdx.x < 64) box.runtaken[threadIdx.x] = 0u;
     __syncthreads();
     const unsigned k = (unsigned)a.k;
     const unsigned row_bytes = (unsigned)KR * 64u * GB;  // granule rows
@@ -827,7 +829,12 @@ __global__ void __launch_bounds__(320) k_bpr_chain3(ChainArgs a, const int32_t *
             len = (unsigned)(e1 - e0 < 0x7fffffff ? e1 - e0 : 0x7fffffff);
             if (more && e1 <= e0) { --rc; continue; }                   // an empty run: nothing to tell anybody
             seq0 = next_seq;
-            {   // the mailbox for L1 (a ring as long as the packet ring: L1 cannot be that many runs behind, see reserve_slow)
+            {   // the mailbox for L1, a ring of kTrioRing runs.  Nothing else bounds how far L1 lags: in runs without a live odd
+                // triplet (one triplet, or every odd negative skipped) L1 publishes nothing, so the packet ring (reserve_slow)
+                // never waits for it.  The slot of run rc held run rc - kTrioRing: write it once L1 has read that one.
+                while ((int)(rc - (unsigned)__builtin_amdgcn_readfirstlane((int)lds_get(&box.runtaken[lane]))) > kTrioRing)
+                    if (!nap()) goto bail;
+                idle = 0;
                 unsigned mb = rc;
                 mb = write_lane<0>(mb, (unsigned)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uint64_t)e0));
                 mb = write_lane<1>(mb, (unsigned)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)e0 >> 32)));
@@ -873,6 +880,8 @@ __global__ void __launch_bounds__(320) k_bpr_chain3(ChainArgs a, const int32_t *
             if (len == 0xffffffffu) break;
             e0 = (int64_t)(((uint64_t)(unsigned)__builtin_amdgcn_readlane((int)mb, 1) << 32) | (unsigned)__builtin_amdgcn_readlane((int)mb, 0));
             seq0 = (unsigned)__builtin_amdgcn_readlane((int)mb, 3);
+            asm volatile("" ::: "memory");
+            lds_put(&box.runtaken[lane], rc);            // behind this wave's read of the slot (LDS order): L0 may reuse it
         }
 
         unsigned seg_seq = seq0 + 1u;                    // number of the segment's first live triplet
