@@ -4,8 +4,8 @@
 usage: python tools/traffic_json.py FETCH.txt WRITE.txt WORKLOAD ROUND_EVENTS "taken ..." > profiles/rNN_traffic.json
 
 FETCH_SIZE is reported in KiB and reads exactly 1/2 of the bytes on gfx950 for these 4-byte-per-lane loads: the correction
-factor is calibrated in the same pass on k_sumsq, whose bytes are known (it reads P then Q once: the larger of its two
-launches reads m * k * 4 bytes -- passed as CALIBRATION_BYTES, default the C3 user factors).  WRITE_SIZE (KiB) is exact
+factor is calibrated in the same pass on k_sumsq, whose bytes are known (it reads Q once per epoch, and P too unless the
+update launches summed P*P: the mean bytes per launch can be passed as CALIBRATION_BYTES, default the C3 factors).  WRITE_SIZE (KiB) is exact
 for stores and float atomics."""
 import json
 import os
@@ -43,9 +43,12 @@ def main():
     fetch = {upd: f[km]['FETCH_SIZE'][0], 'k_round_fold': f[kf]['FETCH_SIZE'][0]}
     write = {upd: w[pick(w, upd + '<')]['WRITE_SIZE'][0], 'k_round_fold': w[pick(w, 'k_round_fold<')]['WRITE_SIZE'][0]}
     atomics = w[pick(w, upd + '<')].get('TCC_EA0_ATOMIC_sum', (0.0, 0))[0]
-    # calibration: k_sumsq reads the user factors and the item factors once each (two launches per epoch, averaged here)
-    cal_bytes = float(os.environ.get('CALIBRATION_BYTES', (1000000 + 200000) * 128 * 4 / 2))
-    cal_kib = f[pick(f, 'k_sumsq')]['FETCH_SIZE'][0]
+    # calibration: k_sumsq reads the item factors once per epoch, and the user factors too (two launches per epoch, averaged
+    # here) unless the epoch's update launches summed P*P themselves (one launch per epoch; epochs = k_sample's launches)
+    sumsq = f[pick(f, 'k_sumsq')]['FETCH_SIZE']
+    per_epoch = sumsq[1] / f[pick(f, 'k_sample')]['FETCH_SIZE'][1]
+    cal_bytes = float(os.environ.get('CALIBRATION_BYTES', (1000000 + 200000) * 128 * 4 / 2 if per_epoch > 1.5 else 200000 * 128 * 4))
+    cal_kib = sumsq[0]
     corr = cal_bytes / 1024.0 / cal_kib
     traffic = (fetch[upd] + fetch['k_round_fold']) * 1024.0 * round(corr) + (write[upd] + write['k_round_fold']) * 1024.0
     print(json.dumps({

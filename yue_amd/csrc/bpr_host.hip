@@ -279,6 +279,7 @@ int launch_round_m(yue_ctx *c, const yue::TrainArgs &a_in, int64_t e0, int64_t e
 int launch_round_u(yue_ctx *c, const yue::TrainArgs &a, int64_t u0, int64_t u1, int64_t e0, int64_t e1, int64_t round_index) {
     yue::RoundUArgs ra{};
     ra.u_begin = u0; ra.u_end = u1; ra.ev_ptr = c->d_ev_ptr.p; ra.e_begin = e0; ra.e_end = e1; ra.staged = c->staged ? 1 : 0; ra.margins = c->margins.p;
+    ra.psq_slots = c->psq_in_rounds ? c->psq_slots.p : nullptr;
     const int64_t blocks = (u1 - u0 + 3) / 4;
     if (blocks == 0) return YUE_OK;
     const dim3 grid((unsigned)blocks), block(256);
@@ -407,10 +408,11 @@ int read_scalars(yue_ctx *c, double *nll, double *sp, double *sq) {
     return YUE_OK;
 }
 
-int sumsq_async(yue_ctx *c) {
+int sumsq_async(yue_ctx *c, const double *p_slots) {
     double *sc = c->scal.p + yue::kNllSlots;
     HIPCHK(hipMemsetAsync(sc + 1, 0, 2 * sizeof(double), c->stream));
-    hipLaunchKernelGGL(yue::k_sumsq, dim3(2048), dim3(256), 0, c->stream, c->P.p, c->m * c->k, sc + 1);
+    if (p_slots) hipLaunchKernelGGL(yue::k_sum_slots, dim3(1), dim3(64), 0, c->stream, p_slots, yue::kNllSlots, sc + 1);
+    else hipLaunchKernelGGL(yue::k_sumsq, dim3(2048), dim3(256), 0, c->stream, c->P.p, c->m * c->k, sc + 1);
     hipLaunchKernelGGL(yue::k_sumsq, dim3(2048), dim3(256), 0, c->stream, c->Q.p, c->n * c->k, sc + 2);
     return YUE_OK;
 }
@@ -673,6 +675,12 @@ int yue_bpr_epoch(yue_ctx *c, uint64_t seed, uint32_t epoch, int64_t round_event
         }
         HIPCHK(c->margins.resize((size_t)std::max<int64_t>(E, 1)));
     }
+    // every user stores P[u] exactly once in k_round_u: the waves sum P*P there, the epoch skips its pass over P
+    c->psq_in_rounds = seq_user && c->all_users_have_events && E > 0;
+    if (c->psq_in_rounds) {
+        HIPCHK(c->psq_slots.resize((size_t)yue::kNllSlots));
+        HIPCHK(hipMemsetAsync(c->psq_slots.p, 0, (size_t)yue::kNllSlots * sizeof(double), c->stream));
+    }
     c->last_round_user_seq = 0;
     auto after = [&](int64_t r) -> int {
         if (seq_user && !c->bigq) { c->last_round_user_seq = 1; return YUE_OK; }          // (bigq is set by run_rounds before the first round)
@@ -699,6 +707,10 @@ int yue_bpr_epoch(yue_ctx *c, uint64_t seed, uint32_t epoch, int64_t round_event
     if ((rc = run_rounds(c, a, bounds, 0, after, meta_path_fits(c), seq_user ? &ublock : nullptr))) { reset_round_state(c); return rc; }
     if (c->last_round_user_seq && E > 0)      // the loss of the epoch from the margins k_round_u left
         hipLaunchKernelGGL(yue::k_loss_margins, dim3(2048), dim3(256), 0, c->stream, c->margins.p, c->ev_j.p, E, c->scal.p);
+    // (k_round_u path: P*P was summed in the rounds when every user has events -- unless the item matrix took the BIGQ form,
+    // whose rounds keep user rows in dP)
+    const bool psq_done = c->psq_in_rounds && c->last_round_user_seq;
+    c->psq_in_rounds = false;
     // the epoch's user rows must be complete before the loss sums and before the next epoch reads P
     if (yue_host::on_communicator(c)) {       // how long the compute stream has to wait for the last group's all-reduce + apply
         HIPCHK(hipEventRecord(c->ev_t_rounds, c->stream));
@@ -708,7 +720,7 @@ int yue_bpr_epoch(yue_ctx *c, uint64_t seed, uint32_t epoch, int64_t round_event
     HIPCHK(hipStreamWaitEvent(c->stream, c->ev_comm, 0));      // the ONLY wait of the compute stream for the collective stream in an epoch
     c->comm_compute_waits = 1;
     HIPCHK(hipGetLastError());
-    if ((rc = sumsq_async(c))) return rc;
+    if ((rc = sumsq_async(c, psq_done ? c->psq_slots.p : nullptr))) return rc;
     if ((rc = read_scalars(c, nll_out, sumsqP_out, sumsqQ_out))) return rc;
     if (yue_host::on_communicator(c)) {
         float ms = 0.f;

@@ -150,6 +150,8 @@ int yue_set_interactions(yue_ctx *c, const int64_t *indptr, const int32_t *indic
         }
     c->E = E; c->nnz = nnz;
     c->h_ev_ptr.assign(ev_ptr, ev_ptr + m + 1);
+    c->all_users_have_events = true;
+    for (int64_t u = 0; u < m; ++u) if (ev_ptr[u + 1] <= ev_ptr[u]) { c->all_users_have_events = false; break; }
     c->d_ev_ptr_valid = false;
     HIPCHK(c->indptr.resize(m + 1)); HIPCHK(c->indices.resize(std::max<int64_t>(nnz, 1)));
     HIPCHK(c->ev_u.resize((size_t)E + yue_host::kHeaderSlackHost)); HIPCHK(c->ev_i.resize((size_t)E + yue_host::kHeaderSlackHost)); HIPCHK(c->ev_j.resize((size_t)E + yue_host::kHeaderSlackHost));   // (+ slack: k_round_m reads whole header blocks)

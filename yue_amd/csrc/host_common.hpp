@@ -66,6 +66,7 @@ struct yue_ctx {
     bool have_factors = false, have_inter = false;
     DevBuf<float> P, Q, dP, dQ;
     DevBuf<float> margins;                       // [E] the events' margins of the running epoch (k_round_u -> k_loss_margins)
+    DevBuf<double> psq_slots;                    // [kNllSlots] sum P*P of the users k_round_u stored (the epoch's P pass when every user has events)
     DevBuf<unsigned long long> cnt0, cnt1;       // item-row touch counters of the even / odd round (total | remaining)
     DevBuf<uint32_t> cntp0, cntp1;               // user-row flushes of the even / odd round
     DevBuf<uint32_t> tab0, tab1;                 // staging-slot tables of the even / odd round (kStageMax words per item row)
@@ -92,6 +93,8 @@ struct yue_ctx {
     int64_t adam_m = 0, adam_n = 0; int adam_k = 0;
     DevBuf<double> scal;                 // [kNllSlots] nll slots + [8] scalars
     std::vector<int64_t> h_ev_ptr;       // host copy: user -> first event
+    bool all_users_have_events = false;  // every user of h_ev_ptr has at least one event
+    bool psq_in_rounds = false;          // yue_bpr_epoch: k_round_u sums P*P into psq_slots
     // scoring scratch
     DevBuf<int32_t> s_users, s_ids, s_mask_idx, s_flags;
     DevBuf<int32_t> s_few, s_few_ids;   // two-phase scoring: positions / ids of the users with fewer than N candidates in the first chunk, their lists
@@ -195,7 +198,7 @@ inline bool on_communicator(const yue_ctx *c) { return c->comm != nullptr || c->
 // bpr_host.hip: loss / scalar scratch shared by the training entry points
 int zero_scalars(yue_ctx *c);
 int read_scalars(yue_ctx *c, double *nll, double *sp, double *sq);
-int sumsq_async(yue_ctx *c);
+int sumsq_async(yue_ctx *c, const double *p_slots = nullptr);   // p_slots: sum P*P from these kNllSlots partial sums instead of a pass over P
 int upload_triplets(yue_ctx *c, const int32_t *u, const int32_t *i, const int32_t *j, int64_t T, bool validate);
 // comm.hip: sum dP[first .. first + count) over the ranks on `stream` (in place); identity without a communicator
 int reduce_user_block(yue_ctx *c, int64_t first, int64_t count, hipStream_t stream);

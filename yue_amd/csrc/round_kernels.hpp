@@ -10,7 +10,8 @@
 //   k_round_m      reads the metadata, gathers, updates, stores (in place / to the touch's staging row base + ticket / float
 //                  atomics for hot rows) and ends: no wave waits for another, a launch may be several wave generations;
 //   k_round_fold   the next launch on the stream -- the kernel boundary is the synchronisation -- rewrites the round's
-//                  contended rows from the list: row += its block of staged differences in ticket order.
+//                  contended rows from the list: row = its staged block summed in ticket order (ticket 0 staged its new
+//                  row, the others their differences).
 #pragma once
 #include "train_kernels.hpp"
 
@@ -51,18 +52,32 @@ namespace yue {
 // Metadata word of one touch (an event's positive or negative item row) in its round:
 //   bits 0..1   kind: 0 no touch (the sampler gave up on the event), 1 the round's only touch of the row (stored in place),
 //               2 staged (the row has 2..stage_max touches), 3 hot (hotter: float atomics into dQ)
-//   bits 2..31  staged: THIS touch's staging row (first row of the row's block + the touch's ticket)
+//   bits 2..30  staged: THIS touch's staging row (first row of the row's block + the touch's ticket)
+//   bit 31      staged: the touch holds ticket 0 (the block's first row): it stores its NEW row there, every other touch
+//               of the block stores (new - old) -- the fold then sums the block and never reads the round-start row
 // Fold-list word of a contended row:
 //   bits 25..31 staged: the row's touches = rows of its block (2..kMetaStageMax); 0: hot
 //   bits 0..24  staged: first staging row of the block
 constexpr uint32_t kMetaStageMax = 64u;  // largest block (7-bit count field)
 constexpr uint32_t kMetaStageDefault = 4u;   // measured on C3 (k = 128): staging rows with 5..8 touches too is slower (34.0 vs 33.2 ms/epoch)
 constexpr uint32_t kMetaUnique = 1u, kMetaStaged = 2u, kMetaHot = 3u;
+constexpr uint32_t kMetaFirst = 1u << 31;
 constexpr int kMetaUnroll = 8;       // events per thread and step of k_round_meta's two sweeps (their loads are in flight together)
 __host__ __device__ inline uint32_t meta_kind(uint32_t w) { return w & 3u; }
-__host__ __device__ inline uint32_t meta_slot(uint32_t w) { return w >> 2; }
+__host__ __device__ inline uint32_t meta_slot(uint32_t w) { return (w >> 2) & 0x1fffffffu; }
+__host__ __device__ inline bool meta_first(uint32_t w) { return (w & kMetaFirst) != 0u; }
 __host__ __device__ inline uint32_t fold_count(uint32_t w) { return w >> 25; }
 __host__ __device__ inline uint32_t fold_block(uint32_t w) { return w & 0x1ffffffu; }
+// k_round_meta's LDS word of a staged row while it hands out the block's rows: bit 31 set, bits 25..30 the next ticket,
+// bits 0..24 the block's first staging row (one LDS atomic per touch returns both; a unique or hot row's word is its
+// metadata word, bit 31 clear).  Tickets stay below kMetaStageMax = 64: the field carries into bit 31 only after a block's
+// last touch has taken its row.
+constexpr uint32_t kLdsStaged = 1u << 31, kLdsTicket = 1u << 25;
+static_assert(kMetaStageMax <= 64u, "tickets of a block must fit bits 25..30 of the LDS word");
+__device__ inline uint32_t meta_of_staged(uint32_t lds) {
+    const uint32_t ticket = (lds >> 25) & 63u;
+    return kMetaStaged | (((lds & 0x1ffffffu) + ticket) << 2) | (ticket == 0u ? kMetaFirst : 0u);
+}
 
 struct MetaArgs {
     const int32_t *ev_i, *ev_j;
@@ -169,7 +184,7 @@ __global__ void __launch_bounds__(1024) k_round_meta(MetaArgs a) {
                 const uint32_t c = slots[s];
                 if (c >= 2u) {
                     const bool st = c <= a.stage_max;
-                    slots[s] = st ? (kMetaStaged | ((uint32_t)run << 2)) : kMetaHot;
+                    slots[s] = st ? (kLdsStaged | ((uint32_t)run & 0x1ffffffu)) : kMetaHot;
                     fold[run >> 32] = make_uint2((uint32_t)(lo + s), st ? ((c << 25) | ((uint32_t)run & 0x1ffffffu)) : 0u);
                     run += (1ull << 32) + (st ? c : 0u);
                 }
@@ -182,7 +197,7 @@ __global__ void __launch_bounds__(1024) k_round_meta(MetaArgs a) {
                 const uint2 tc = mine_t[t];
                 const uint32_t sl = tc.x - (uint32_t)lo;
                 const uint32_t wd = slots[sl];
-                const uint32_t mw = meta_kind(wd) == kMetaStaged ? atomicAdd(&slots[sl], 4u) : wd;
+                const uint32_t mw = (wd & kLdsStaged) ? meta_of_staged(atomicAdd(&slots[sl], kLdsTicket)) : wd;
                 ((tc.y & 1u) ? a.meta_j : a.meta_i)[e0 + (tc.y >> 1)] = mw;
             }
         } else
@@ -198,14 +213,14 @@ __global__ void __launch_bounds__(1024) k_round_meta(MetaArgs a) {
                 const int64_t e = eb + 1024 * q;
                 if (vj[q] >= 0) {
                     const uint32_t si = (uint32_t)(vi[q] - lo), sj = (uint32_t)(vj[q] - lo);
-                    // a staged row's word hands out the block's rows: every touch takes the next one
+                    // a staged row's word hands out the block's rows: every touch takes the next ticket
                     if (si < (uint32_t)width) {
                         const uint32_t wd = slots[si];
-                        a.meta_i[e] = meta_kind(wd) == kMetaStaged ? atomicAdd(&slots[si], 4u) : wd;
+                        a.meta_i[e] = (wd & kLdsStaged) ? meta_of_staged(atomicAdd(&slots[si], kLdsTicket)) : wd;
                     }
                     if (sj < (uint32_t)width) {
                         const uint32_t wd = slots[sj];
-                        a.meta_j[e] = meta_kind(wd) == kMetaStaged ? atomicAdd(&slots[sj], 4u) : wd;
+                        a.meta_j[e] = (wd & kLdsStaged) ? meta_of_staged(atomicAdd(&slots[sj], kLdsTicket)) : wd;
                     }
                 } else if (g == 0 && e < e1) {
                     a.meta_i[e] = 0u; a.meta_j[e] = 0u;
@@ -289,7 +304,8 @@ struct RoundMArgs {
 
 // The S-round update launch on pre-pass metadata.  Update semantics, arithmetic and the three kinds of row stores are those
 // of k_round; user rows always stay in dP (the epoch path applies them per group of rounds).  The launch ends behind its
-// stores: the round's contended rows are rewritten by k_round_fold.
+// stores: the round's contended rows are rewritten by k_round_fold (ticket 0 of a staged block stores its new row, the
+// other touches (new - old)).
 // At most 96 SGPRs: a CU then holds 7 workgroups of this kernel (floor(800 / (96 + 16)); with the 106 the compiler would
 // take it is 6, whatever the register-file arithmetic says -- DESIGN.md section 5); the excess lives in VGPR lanes.
 // BIGQ: item matrices (+ staging rows) of 2 GiB and more -- the item rows, the staging rows and dQ are addressed through 64-bit
@@ -408,6 +424,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) k_ro
         const unsigned cli = meta_kind(hmi[t]), clj = meta_kind(hmj[t]);
         const bool uniq_i = cli == kMetaUnique, uniq_j = clj == kMetaUnique;
         const bool hot_i = cli == kMetaHot, hot_j = clj == kMetaHot;
+        // the new row (only touch of the round, or ticket 0 of a staged block) or (new - old)
+        const bool full_i = uniq_i || meta_first(hmi[t]), full_j = uniq_j || meta_first(hmj[t]);
         // where the row's store goes: the row itself (only touch of the round) or the touch's staging row
         const unsigned wi = uniq_i ? oi[t] : stage0 + meta_slot(hmi[t]) * row_bytes;
         const unsigned wj = uniq_j ? oj[t] : stage0 + meta_slot(hmj[t]) * row_bytes;
@@ -416,8 +434,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) k_ro
             Elem o[KR];
 #pragma unroll
             for (int r = 0; r < KR; ++r) { o[r] = bpr_elem(p[t][r], qi[t][r], qj[t][r], c, a.ru, a.ri); dp[r] += o[r].p2 - p[t][r]; }
-            // the new row in place, or (new - old) to the staging row: one store, value and offset selected; a hot row's
-            // difference goes into dQ with float atomics (one wave-uniform branch per touch)
+            // the new row in place or to ticket 0's staging row, else (new - old) to the staging row: one store, value and
+            // offset selected; a hot row's difference goes into dQ with float atomics (one wave-uniform branch per touch)
             if (BIGQ) {
                 const uint64_t ri_ = (uint64_t)(unsigned)hi_[t] * k, rj_ = (uint64_t)(unsigned)hj[t] * k;
                 float *di = hot_i ? a.dQ + ri_ : uniq_i ? a.Q + ri_ : a.stage + (uint64_t)meta_slot(hmi[t]) * k;
@@ -425,21 +443,21 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) k_ro
 #pragma unroll
                 for (int r = 0; r < KR; ++r) {
                     if (ev[r]) {
-                        if (hot_i) unsafeAtomicAdd(di + el[r], o[r].qi2 - qi[t][r]); else di[el[r]] = uniq_i ? o[r].qi2 : o[r].qi2 - qi[t][r];
-                        if (hot_j) unsafeAtomicAdd(dj + el[r], o[r].qj2 - qj[t][r]); else dj[el[r]] = uniq_j ? o[r].qj2 : o[r].qj2 - qj[t][r];
+                        if (hot_i) unsafeAtomicAdd(di + el[r], o[r].qi2 - qi[t][r]); else di[el[r]] = full_i ? o[r].qi2 : o[r].qi2 - qi[t][r];
+                        if (hot_j) unsafeAtomicAdd(dj + el[r], o[r].qj2 - qj[t][r]); else dj[el[r]] = full_j ? o[r].qj2 : o[r].qj2 - qj[t][r];
                     }
                 }
             } else {
             if (!hot_i) {
 #pragma unroll
-                for (int r = 0; r < KR; ++r) YUE_BSTORE(uniq_i ? o[r].qi2 : o[r].qi2 - qi[t][r], rsQ, vo[r], wi);
+                for (int r = 0; r < KR; ++r) YUE_BSTORE(full_i ? o[r].qi2 : o[r].qi2 - qi[t][r], rsQ, vo[r], wi);
             } else {
 #pragma unroll
                 for (int r = 0; r < KR; ++r) YUE_M_HOT(o[r].qi2 - qi[t][r], rsdQ, vo[r], oi[t]);
             }
             if (!hot_j) {
 #pragma unroll
-                for (int r = 0; r < KR; ++r) YUE_BSTORE(uniq_j ? o[r].qj2 : o[r].qj2 - qj[t][r], rsQ, vo[r], wj);
+                for (int r = 0; r < KR; ++r) YUE_BSTORE(full_j ? o[r].qj2 : o[r].qj2 - qj[t][r], rsQ, vo[r], wj);
             } else {
 #pragma unroll
                 for (int r = 0; r < KR; ++r) YUE_M_HOT(o[r].qj2 - qj[t][r], rsdQ, vo[r], oj[t]);
@@ -477,13 +495,17 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) k_ro
 // Oracle: oracle/bpr_oracle.c: orc_bpr_rounds_seq_user (a round of one event = the reference's loop).
 // FAST: the step's coefficient in single precision (chain_coef_fast: five instructions instead of ~35 double-precision ones on
 // all lanes -- k_round_m computes eight sigmoids at once in the lanes, a chain of dependent events cannot).  The loss is summed
-// from double-precision sigmoids of the events' margins, which this kernel leaves in a buffer for k_loss_margins (one pass per epoch).
+// from double-precision sigmoids of the events' margins, which this kernel leaves in a buffer for k_loss_margins (one pass per
+// epoch; the double-precision code inside this kernel takes 79 instead of 39 VGPRs at k = 128, summed in the fold launch it
+// costs that launch a wave per SIMD: both measured slower).  psq_slots: the wave also adds sum P[u]*P[u] of the row it stores
+// (BPR.py:59, fp32 squares summed in double as k_sumsq does), so that the epoch needs no pass over P when every user has events.
 struct RoundUArgs {
     int64_t u_begin, u_end;      // users of the round: one wave each
     const int64_t *ev_ptr;       // [m + 1] first event of a user
     int64_t e_begin, e_end;      // events of the round (size of the staging area)
     int staged;
     float *margins;              // [E] the events' margins x (BPR.py:50), for the loss (k_loss_margins)
+    double *psq_slots;           // [kNllSlots] or null
 };
 
 template <int KR, bool FAST>
@@ -524,7 +546,7 @@ __global__ void __launch_bounds__(256) k_round_u(TrainArgs a, RoundUArgs ra, con
             if (!ex) { hI = 0; hJ = -1; hMI = 0u; hMJ = 0u; }
         }
         const unsigned seg_len = len - seg < 64u ? len - seg : 64u;
-        float xs = 0.0f;                                 // lane t keeps the margin of the segment's event t (the loss is summed from them by k_loss_margins: no double-precision code in this kernel)
+        float xs = 0.0f;                                 // lane t keeps the margin of the segment's event t (the loss is summed from them by k_loss_margins: no double-precision code in this kernel's loop)
         // the two item rows of an event, gathered D events ahead of the arithmetic
         auto gather = [&](float (&qi)[KR], float (&qj)[KR], unsigned t) {
             const int ti = __builtin_amdgcn_readlane(hI, t), tj = __builtin_amdgcn_readlane(hJ, t);
@@ -546,6 +568,8 @@ __global__ void __launch_bounds__(256) k_round_u(TrainArgs a, RoundUArgs ra, con
             xs = (unsigned)lane == t ? x : xs;
             const unsigned cli = meta_kind(mi), clj = meta_kind(mj);
             const bool uniq_i = cli == kMetaUnique, uniq_j = clj == kMetaUnique;
+            // the new row (only touch of the round, or ticket 0 of a staged block) or (new - old)
+            const bool full_i = uniq_i || meta_first(mi), full_j = uniq_j || meta_first(mj);
             const unsigned oi = (unsigned)ti * row_bytes, oj = (unsigned)tj * row_bytes;
             // where the row's store goes: the row itself (only touch of the round) or the touch's staging row
             const unsigned wi = uniq_i ? oi : stage0 + meta_slot(mi) * row_bytes;
@@ -555,14 +579,14 @@ __global__ void __launch_bounds__(256) k_round_u(TrainArgs a, RoundUArgs ra, con
             for (int r = 0; r < KR; ++r) { o[r] = bpr_elem(p[r], qi[r], qj[r], c, a.ru, a.ri); p[r] = o[r].p2; }   // BPR.py:51-57; the user row moves on
             if (cli != kMetaHot) {
 #pragma unroll
-                for (int r = 0; r < KR; ++r) YUE_BSTORE(uniq_i ? o[r].qi2 : o[r].qi2 - qi[r], rsQ, vo[r], wi);
+                for (int r = 0; r < KR; ++r) YUE_BSTORE(full_i ? o[r].qi2 : o[r].qi2 - qi[r], rsQ, vo[r], wi);
             } else {
 #pragma unroll
                 for (int r = 0; r < KR; ++r) YUE_M_HOT(o[r].qi2 - qi[r], rsdQ, vo[r], oi);
             }
             if (clj != kMetaHot) {
 #pragma unroll
-                for (int r = 0; r < KR; ++r) YUE_BSTORE(uniq_j ? o[r].qj2 : o[r].qj2 - qj[r], rsQ, vo[r], wj);
+                for (int r = 0; r < KR; ++r) YUE_BSTORE(full_j ? o[r].qj2 : o[r].qj2 - qj[r], rsQ, vo[r], wj);
             } else {
 #pragma unroll
                 for (int r = 0; r < KR; ++r) YUE_M_HOT(o[r].qj2 - qj[r], rsdQ, vo[r], oj);
@@ -585,6 +609,14 @@ __global__ void __launch_bounds__(256) k_round_u(TrainArgs a, RoundUArgs ra, con
     }
 #pragma unroll
     for (int r = 0; r < KR; ++r) { const unsigned e = 64u * r + lane; if (e < k) prow[e] = p[r]; }
+    if (ra.psq_slots) {
+        double s = 0.0;
+#pragma unroll
+        for (int r = 0; r < KR; ++r) { const unsigned e = 64u * r + lane; const float sq = p[r] * p[r]; if (e < k) s += (double)sq; }
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) s += __shfl_xor(s, off);
+        if (lane == 0) atomicAdd(ra.psq_slots + (u & (kNllSlots - 1)), s);
+    }
 }
 
 // sum over the events with a negative of -log(sigmoid(margin)) (BPR.py:58), double precision, into the loss slots
@@ -598,9 +630,10 @@ __global__ void __launch_bounds__(256) k_loss_margins(const float *__restrict__ 
     if ((threadIdx.x & 63) == 0 && nl != 0.0) atomicAdd(nll_slots + ((blockIdx.x * 4 + (threadIdx.x >> 6)) & (kNllSlots - 1)), nl);
 }
 
-// Rewrites the contended item rows of one round from the pre-pass's fold list: row += the block of staged differences in
-// ticket order, or += the row of dQ (zeroed again) for a hot row.  A wave takes EPG consecutive list entries at a time
-// (rows of neighbouring items: their staging blocks lie behind each other), all loads before the first store.
+// Rewrites the contended item rows of one round from the pre-pass's fold list: row = the sum of its staged block in ticket
+// order (ticket 0 holds the touch's new row, the others (new - old): the round-start row is not read), or row += the row
+// of dQ (zeroed again) for a hot row.  A wave takes EPG consecutive list entries at a time (rows of neighbouring items:
+// their staging blocks lie behind each other), all loads before the first store.
 struct FoldArgs {
     const uint2 *fold;                     // this round's entries (16-byte aligned)
     const unsigned long long *round_rows;  // this round's counters (high half: entries)
@@ -613,9 +646,9 @@ struct FoldArgs {
 template <int KR, int EPG>
 __device__ __forceinline__ void fold_group(const FoldArgs &f, int lane, unsigned k, uint32_t nact, const uint2 (&ent)[4]) {
     // straight-line loads (no wait between the entries): the first two rows of a block always (a hot row reads its row of
-    // dQ), rows 2..3 behind a wave-uniform branch on the row's touch count; lanes beyond k read element k - 1.  Larger
-    // blocks (rows 4..) are summed behind the stores of the group, four rows at a time.
-    float x[EPG][KR], st[EPG][4][KR];
+    // dQ and the item row itself), rows 2..3 behind a wave-uniform branch on the row's touch count; lanes beyond k read
+    // element k - 1.  Larger blocks (rows 4..) are summed behind the stores of the group, four rows at a time.
+    float st[EPG][4][KR];
     unsigned el[KR];
     bool big = false;
 #pragma unroll
@@ -625,10 +658,17 @@ __device__ __forceinline__ void fold_group(const FoldArgs &f, int lane, unsigned
         if ((uint32_t)sl >= nact) continue;
         const uint32_t c = fold_count(ent[sl].y);
         const bool hot = c == 0u;
-        const float *row = f.Q + (uint64_t)ent[sl].x * k;
         const float *src = hot ? f.dQ + (uint64_t)ent[sl].x * k : f.stage + (uint64_t)fold_block(ent[sl].y) * k;
 #pragma unroll
-        for (int r = 0; r < KR; ++r) { st[sl][0][r] = YUE_FOLD_LD(src + el[r]); if (!hot) st[sl][1][r] = YUE_FOLD_LD(src + (uint64_t)k + el[r]); }
+        for (int r = 0; r < KR; ++r) st[sl][0][r] = YUE_FOLD_LD(src + el[r]);
+        if (hot) {
+            const float *row = f.Q + (uint64_t)ent[sl].x * k;
+#pragma unroll
+            for (int r = 0; r < KR; ++r) st[sl][1][r] = YUE_FOLD_LDROW(row + el[r]);
+        } else {
+#pragma unroll
+            for (int r = 0; r < KR; ++r) st[sl][1][r] = YUE_FOLD_LD(src + (uint64_t)k + el[r]);
+        }
         if (c > 2u) {
 #pragma unroll
             for (unsigned q = 2; q < 4; ++q)
@@ -636,8 +676,6 @@ __device__ __forceinline__ void fold_group(const FoldArgs &f, int lane, unsigned
                 for (int r = 0; r < KR; ++r) st[sl][q][r] = YUE_FOLD_LD(src + (uint64_t)(q < c ? q : 0u) * k + el[r]);
         }
         big = big || c > 4u;
-#pragma unroll
-        for (int r = 0; r < KR; ++r) x[sl][r] = YUE_FOLD_LDROW(row + el[r]);
     }
 #pragma unroll
     for (int sl = 0; sl < EPG; ++sl) {
@@ -648,12 +686,17 @@ __device__ __forceinline__ void fold_group(const FoldArgs &f, int lane, unsigned
         float *dr = f.dQ + (uint64_t)ent[sl].x * k;
 #pragma unroll
         for (int r = 0; r < KR; ++r) {
+            // staged: the differences of tickets 1.. in ticket order, then ticket 0's new row (the round-start row takes
+            // part in one rounding less than in a running sum); hot: the row plus its row of dQ
             const unsigned e = 64u * r + lane;
-            float acc = st[sl][0][r];
+            float acc = st[sl][1][r];
 #pragma unroll
-            for (unsigned q = 1; q < 4; ++q) { const float v = q < c ? st[sl][q][r] : 0.0f; acc = acc + v; }
-            st[sl][0][r] = acc;
-            if (c <= 4u && e < k) { row[e] = x[sl][r] + acc; if (hot) dr[e] = 0.0f; }
+            for (unsigned q = 2; q < 4; ++q) { const float v = q < c ? st[sl][q][r] : 0.0f; acc = acc + v; }
+            st[sl][1][r] = acc;
+            if (c <= 4u && e < k) {
+                row[e] = st[sl][0][r] + acc;
+                if (hot) dr[e] = 0.0f;
+            }
         }
     }
     if (big) {                                           // wave-uniform; the rest of a large block in ticket order
@@ -666,7 +709,7 @@ __device__ __forceinline__ void fold_group(const FoldArgs &f, int lane, unsigned
             float *row = f.Q + (uint64_t)ent[sl].x * k;
             float acc[KR];
 #pragma unroll
-            for (int r = 0; r < KR; ++r) acc[r] = st[sl][0][r];
+            for (int r = 0; r < KR; ++r) acc[r] = st[sl][1][r];
             constexpr unsigned STEP = KR == 1 ? 8u : 4u;      // rows in flight per step (k <= 64: blocks are long, rows short)
             for (uint32_t q0 = 4u; q0 < c; q0 += STEP) {
                 float v[STEP][KR];
@@ -680,14 +723,14 @@ __device__ __forceinline__ void fold_group(const FoldArgs &f, int lane, unsigned
                     for (int r = 0; r < KR; ++r) acc[r] = acc[r] + (q0 + q < c ? v[q][r] : 0.0f);
             }
 #pragma unroll
-            for (int r = 0; r < KR; ++r) { const unsigned e = 64u * r + lane; if (e < k) row[e] = x[sl][r] + acc[r]; }
+            for (int r = 0; r < KR; ++r) { const unsigned e = 64u * r + lane; if (e < k) row[e] = st[sl][0][r] + acc[r]; }
         }
     }
 }
 
 template <int KR>
 __global__ void __launch_bounds__(256) k_round_fold(FoldArgs f) {
-    constexpr int EPG = KR == 4 ? 2 : 4;                // list entries per group (register budget: EPG * 5 * KR row registers)
+    constexpr int EPG = KR == 4 ? 2 : 4;                // list entries per group (register budget: EPG * 4 * KR row registers)
     const int lane = threadIdx.x & 63;
     const uint32_t wave = blockIdx.x * 4u + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint32_t nwaves = gridDim.x * 4u;
