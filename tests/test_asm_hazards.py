@@ -6,7 +6,12 @@ look into: round 3 had two memory-access faults from exactly this (a descriptor 
 buffer_load).  Every such operand now passes through vmem_sgpr_guard() (an s_nop 4); this test reads the device listing of
 chain_host.hip and fails if any buffer_/global_/flat_ instruction reads an SGPR written by a VALU instruction fewer than 5
 wait states earlier.  (Straight-line scan: a writer on another path into a label is not seen -- the guard sits directly in
-front of the memory instructions, so the fall-through path is the one that matters.)"""
+front of the memory instructions, so the fall-through path is the one that matters.)
+
+The scoring filter's DMA form (k_scan_filter<.., DMA = true>, score2_kernels.hpp) has a hazard of the same kind: its item rows go
+from global memory straight into LDS (buffer_load ... lds), and the workgroup barrier that hands a stage over to the MFMA reads
+is only correct behind an s_waitcnt vmcnt(0) -- which today comes from where the compiler places its own waits, not from the
+source.  The last test pins that on the device listing of scan_host.hip."""
 import os
 import re
 import shutil
@@ -124,3 +129,73 @@ def test_exact_path_listing_has_no_valu_sgpr_to_vmem_hazard(tmp_path):
     assert not bad, bad[:10]
     wide = scan_wide_stores(text)
     assert text.count('buffer_store_dwordx4') > 50 and not wide, wide[:10]
+
+
+LDS_LOAD = re.compile(r'^(buffer_load_\S+\s.*\blds\b|global_load_lds_)')
+
+
+def scan_lds_dma(body):
+    """One function's listing -> (LDS-writing loads, barriers, [(line, barrier, first un-waited load)]): a load that writes LDS
+    (buffer_load_* ... lds, global_load_lds_*) is outstanding until an s_waitcnt that contains vmcnt(0); no s_barrier may be
+    reached with one outstanding.  (Straight-line scan, as above: what is outstanding at the end of the stage loop still is at
+    its top, which is the conservative reading of the back edge.)"""
+    loads = barriers = 0
+    pending = None
+    bad = []
+    for ln, raw in enumerate(body.splitlines(), 1):
+        line = raw.split(';')[0].strip()
+        if not line or line.endswith(':') or line.startswith('.'):
+            continue
+        if LDS_LOAD.match(line):
+            loads += 1
+            if pending is None:
+                pending = (ln, line)
+        elif line.startswith('s_waitcnt') and 'vmcnt(0)' in line:
+            pending = None
+        elif line.split()[0] == 's_barrier':
+            barriers += 1
+            if pending is not None:
+                bad.append((ln, line, pending))
+    return loads, barriers, bad
+
+
+def dma_filter_functions(listing):
+    """name -> body of every k_scan_filter<K16, 4, 2, SETTLE, DMA = true> in a device listing."""
+    out = {}
+    for m in re.finditer(r'^(_ZN3yue13k_scan_filterI\w*Lb1EEEvNS_10FilterArgsE):.*?^\.Lfunc_end\d+:', listing, re.M | re.S):
+        out[m.group(1)] = m.group(0)
+    return out
+
+
+def test_dma_checker_sees_an_unwaited_load_in_front_of_a_barrier():
+    ok = "\tbuffer_load_dwordx4 v7, s[44:47], s3 offen lds\n\tv_mov_b32_e32 v5, v1\n\ts_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier\n"
+    assert scan_lds_dma(ok) == (1, 1, [])
+    for weaker in ('s_waitcnt vmcnt(1)', 's_waitcnt lgkmcnt(0)', 's_nop 0'):
+        loads, barriers, bad = scan_lds_dma(ok.replace('s_waitcnt vmcnt(0) lgkmcnt(0)', weaker))
+        assert (loads, barriers) == (1, 1) and len(bad) == 1 and bad[0][2][0] == 1, weaker
+    assert scan_lds_dma(ok.replace('buffer_load_dwordx4 v7, s[44:47], s3 offen lds', 'global_load_lds_dwordx4 v[2:3], off').replace('vmcnt(0) ', ''))[2] != []
+    # a load into registers is not the filter's hazard; a barrier behind the wait stays clean across a second barrier
+    assert scan_lds_dma("\tbuffer_load_dwordx4 v[4:7], v9, s[4:7], 0 offen\n\ts_barrier\n") == (0, 1, [])
+    assert scan_lds_dma(ok + "\ts_barrier\n") == (1, 2, [])
+    # the wait of one stage does not cover the next stage's load
+    assert len(scan_lds_dma(ok + "\tbuffer_load_dword v7, s[44:47], s3 offen lds\n\ts_barrier\n")[2]) == 1
+    two = "_ZN3yue13k_scan_filterILi4ELi4ELi2ELb0ELb1EEEvNS_10FilterArgsE: ; @x\n" + ok + ".Lfunc_end7:\n"
+    other = two.replace('Lb0ELb1EEE', 'Lb1ELb0EEE').replace('end7', 'end8')
+    assert list(dma_filter_functions(two + other)) == ['_ZN3yue13k_scan_filterILi4ELi4ELi2ELb0ELb1EEEvNS_10FilterArgsE']
+
+
+def test_dma_filter_waits_for_its_lds_loads_before_every_barrier(tmp_path):
+    hipcc = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
+    src = os.path.join(ROOT, 'yue_amd', 'csrc', 'scan_host.hip')
+    lst = tmp_path / 'scan_host.s'
+    out = subprocess.run([hipcc, '--offload-arch=gfx950', '-O3', '-std=c++17', '-ffp-contract=off', '-S', '--cuda-device-only', '-o', str(lst), src],
+                         capture_output=True, text=True, cwd=os.path.dirname(src))
+    assert out.returncode == 0, out.stderr[-2000:]
+    funcs = dma_filter_functions(lst.read_text())
+    assert len(funcs) == 4, sorted(funcs)                  # k = 64 / 128, with and without the settle check
+    for name, body in funcs.items():
+        loads, barriers, bad = scan_lds_dma(body)
+        print(name, 'LDS loads', loads, 'barriers', barriers)
+        assert loads >= 1 and barriers >= 2, (name, loads, barriers)
+        # (if a later compiler breaks this: an explicit asm volatile("s_waitcnt vmcnt(0)") in front of the stage barrier, ADVICE.md)
+        assert not bad, (name, bad[:5])

@@ -137,8 +137,8 @@ __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu
         float ss = 0.0f;
         for (int e = h * (K / 2); e < (h + 1) * (K / 2); ++e) ss = __builtin_fmaf(prow[e], prow[e], ss);
         ss = lo_bcast(ss) + hi_bcast(ss);
-        mu[b] = __builtin_sqrtf(ss) * (1.01f / 128.0f);        // the margin factors of k_topn_scan_bf16p
-        pn[b] = mu[b] * (128.0f * 1.0001f / 1.01f);
+        mu[b] = __builtin_sqrtf(ss) * (kScanMargin / 128.0f);        // the margin factors of k_topn_scan_bf16p
+        pn[b] = mu[b] * (128.0f * 1.0001f / kScanMargin);
         thr[b] = uvalid[b] ? a.thr_rows[upos[b] * a.N + a.N - 1] : INFINITY;
     }
 

@@ -307,6 +307,15 @@ __global__ void __launch_bounds__(256) k_topn_scan(ScanArgs a) {
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+// The pre-filter's margin in units of 2^-7 ||P_u|| max||Q_tile||: the one constant of all bf16 kernels (here and in
+// score2_kernels.hpp).  A diagnostic build lowers it (make margin-probe, tools/scan_margin_probe.py: the adversarial lists
+// of tests/helpers/bf16_adversary.py must then come out WRONG); the settle norm pn below is derived from mu by the same
+// constant, so such a build moves the margin alone.
+#ifndef YUE_SCAN_MARGIN
+#define YUE_SCAN_MARGIN 1.01f
+#endif
+constexpr float kScanMargin = YUE_SCAN_MARGIN;
+
 // T = tiles whose survivors are re-scored together (the fp32 tiles live in a ring of T + 1 LDS buffers), WAVES = waves
 // (of 32 users) per workgroup.  Per phase of the re-score pipeline a wave runs ONE chain for every user that still has a
 // survivor: the phases of a batch number max over the wave's users of their survivors (+ 1); with the survivors of T
@@ -370,13 +379,13 @@ __global__ void __launch_bounds__(64 * WAVES, 512 / (64 * WAVES)) k_topn_scan_bf
 #pragma unroll
         for (int e = 0; e < KH; ++e) ss = __builtin_fmaf(pf[e], pf[e], ss);
         ss += __shfl_xor(ss, 32);
-        mu = __builtin_sqrtf(ss) * (1.01f / 128.0f);           // 2^-7 ||P_u||, 1 % slack for the norm roundings
+        mu = __builtin_sqrtf(ss) * (kScanMargin / 128.0f);           // 2^-7 ||P_u||, 1 % slack for the norm roundings
     }
     // Cauchy-Schwarz: no exact score of a tile exceeds ||P_u|| * max ||Q_i|| (both rounded up: the chain's own rounding,
     // k * 2^-24 relative, is far inside the 1e-4 slacks).  A full list whose threshold is at or above that bound cannot
     // change in the tile: the wave skips the tile when that holds for all its users, the workgroup stops when it holds
     // for all its users against the largest norm of ALL remaining tiles.
-    const float pn = mu * (128.0f * 1.0001f / 1.01f);
+    const float pn = mu * (128.0f * 1.0001f / kScanMargin);
 
     // item tiles: global -> registers (one tile ahead) -> LDS, float4 granularity
     constexpr int PF4 = (kScanTile * K / 4 + NT - 1) / NT;
@@ -584,9 +593,9 @@ __global__ void __launch_bounds__(64 * WAVES, 512 / (64 * WAVES)) k_topn_scan_bf
 #pragma unroll
         for (int e = 0; e < KH; ++e) ss = __builtin_fmaf(pf[e], pf[e], ss);
         ss = lo_bcast(ss) + hi_bcast(ss);                      // sum of the two halves on both lanes
-        mu = __builtin_sqrtf(ss) * (1.01f / 128.0f);
+        mu = __builtin_sqrtf(ss) * (kScanMargin / 128.0f);
     }
-    const float pn = mu * (128.0f * 1.0001f / 1.01f);
+    const float pn = mu * (128.0f * 1.0001f / kScanMargin);
 
     // one stage = TP consecutive tiles = TP * 32 rows of Q, contiguous in memory
     constexpr int ROWS = TP * kScanTile;
