@@ -282,6 +282,36 @@ int yue_wrmf_set_pairs(yue_ctx *ctx, const int64_t *u_ptr, const int32_t *u_item
 int yue_wrmf_half_sweep(yue_ctx *ctx, int side, double alpha, double reg, double *loss_out);
 
 /*
+ * ExpoMF (reference recommender/advanced/ExpoMF.py; Liang et al., "Modeling User Exposure in Recommendation") -- exposure-
+ * weighted ALS on the context's factors: theta = P (users), beta = Q (items), so yue_scores / yue_topn_scan rank with
+ * beta . theta[u] unchanged.  Needs 1 <= k <= 128 and m, n < 2^26 (otherwise YUE_ERR_ARG, nothing launched).
+ *   yue_expo_set_pairs   the arguments and the upload of yue_wrmf_set_pairs (pairs both ways with counts, the longest-row-first
+ *                        schedule, the long rows' chunks: option "wrmf_long_pairs"); the two solvers share that state.
+ *   yue_expo_set_mu / yue_expo_get_mu   the exposure prior, one fp32 value per item, each inside (0, 1).
+ *   yue_expo_half_sweep  side 0: every theta[u] from beta; side 1: every beta[i] from theta.  Per row r with old value x_r, over
+ *                        every row f_j of the fixed side: s_j = x_r . f_j, pEX_j = sqrt(lam_y pi / 2) exp(-lam_y s_j^2 / 2),
+ *                        A_j = (pEX_j + 1e-8) / (pEX_j + 1e-8 + (1 - mu) / mu), A_j = 1 on the row's pairs;
+ *                        B = sum_j A_j f_j f_j^T + lam*I, a = sum over the pairs of r_j f_j, x = B^-1 a by an fp64 Cholesky
+ *                        factorisation, rounded to fp32 once; rows without pairs become 0.  mu is taken per column j
+ *                        (mu_per_column = 1: required on side 0, allowed on side 1 only when m == n, where the reference does
+ *                        exactly that) or per row r (side 1).  The dense sum runs on the matrix cores in fp32
+ *                        (v_mfma_f32_32x32x2_f32, exact fp32 products and sums) in row batches whose Gram workspace fits option
+ *                        "expo_gram_mb" (default 512 MiB); the pairs' correction, lam*I, a and the solve are fp64.  A
+ *                        non-positive pivot returns YUE_ERR_ARG naming the (smallest such) row.  Bit-reproducible (no float
+ *                        atomics; every order of summation depends on the shapes only).
+ *   yue_expo_update_mu   mu[i] = (a + A_sum[i] - 1) / (a + b + m - 2), A_sum[i] = sum over all users of A_ui from the current
+ *                        theta, beta and mu (per item); the sums in fp64, mu rounded to fp32 once.
+ * Read-only options: "expo_last_ns" / "expo_last_gram_ns" (device time of the last half-sweep or mu update / of its dense
+ * Gram launches), "expo_last_batches".
+ */
+int yue_expo_set_pairs(yue_ctx *ctx, const int64_t *u_ptr, const int32_t *u_items, const int32_t *u_counts,
+                       const int64_t *i_ptr, const int32_t *i_users, const int32_t *i_counts, int64_t nnz);
+int yue_expo_set_mu(yue_ctx *ctx, const float *mu, int64_t n);
+int yue_expo_get_mu(yue_ctx *ctx, float *mu, int64_t n);
+int yue_expo_half_sweep(yue_ctx *ctx, int side, double lam, double lam_y, int mu_per_column);
+int yue_expo_update_mu(yue_ctx *ctx, double a, double b, double lam_y);
+
+/*
  * UserKNN (reference recommender/cf/UserKNN.py) -- exact user neighbours and neighbourhood ranking.  Needs no factors.
  * A_u is the set of distinct training items of user u; sim(u, v) = 2|A_u & A_v| / |A_u | A_v| (not Jaccard: in [0, 2]).
  *   yue_knn_set_pairs  the distinct (user, item) pairs both ways: user-major (u_ptr[m+1], items ascending within a user,

@@ -26,6 +26,7 @@ SYMBOLS = ['yue_last_error', 'yue_version', 'yue_ctx_create', 'yue_ctx_destroy',
            'yue_default_round_events', 'yue_epoch_plan',
            'yue_fism_set_model', 'yue_fism_get_model', 'yue_fism_epoch', 'yue_fism_rounds', 'yue_fism_scores', 'yue_fism_topn_scan',
            'yue_wrmf_set_pairs', 'yue_wrmf_half_sweep',
+           'yue_expo_set_pairs', 'yue_expo_set_mu', 'yue_expo_get_mu', 'yue_expo_half_sweep', 'yue_expo_update_mu',
            'yue_knn_set_pairs', 'yue_knn_neighbors', 'yue_knn_predict', 'yue_knn_topn',
            'yue_ipf_set_graph', 'yue_ipf_predict', 'yue_ipf_topn']
 
@@ -358,6 +359,37 @@ class Device(object):
         loss = C.c_double()
         self._chk(self._lib.yue_wrmf_half_sweep(self._ctx, C.c_int(side), C.c_double(alpha), C.c_double(reg), C.byref(loss)))
         return loss.value
+
+    # -- ExpoMF (factors: theta = P, beta = Q) ---------------------------------------------------
+    def expo_set_pairs(self, u_ptr, u_items, u_counts, i_ptr, i_users, i_counts):
+        """The pairs of wrmf_set_pairs (the two ALS solvers share the upload, the schedule and the long rows' chunks)."""
+        u_ptr, a = _i64(u_ptr)
+        i_ptr, d = _i64(i_ptr)
+        assert len(u_ptr) == self.m + 1 and len(i_ptr) == self.n + 1, 'expo_set_pairs: pointer sizes must match set_factors (m + 1, n + 1)'
+        nnz = int(u_ptr[-1])
+        assert int(i_ptr[-1]) == nnz and len(u_items) == nnz and len(u_counts) == nnz and len(i_users) == nnz and len(i_counts) == nnz, \
+            'expo_set_pairs: both directions must hold nnz pairs'
+        u_items, b = _i32(u_items if nnz else np.zeros(1, np.int32))
+        u_counts, c = _i32(u_counts if nnz else np.zeros(1, np.int32))
+        i_users, e = _i32(i_users if nnz else np.zeros(1, np.int32))
+        i_counts, f = _i32(i_counts if nnz else np.zeros(1, np.int32))
+        self._chk(self._lib.yue_expo_set_pairs(self._ctx, a, b, c, d, e, f, C.c_int64(nnz)))
+
+    def expo_set_mu(self, mu):
+        mu, p = _f32(mu)
+        self._chk(self._lib.yue_expo_set_mu(self._ctx, p, C.c_int64(len(mu))))
+
+    def expo_get_mu(self):
+        mu = np.empty(self.n, np.float32)
+        self._chk(self._lib.yue_expo_get_mu(self._ctx, mu.ctypes.data_as(C.POINTER(C.c_float)), C.c_int64(self.n)))
+        return mu
+
+    def expo_half_sweep(self, side, lam, lam_y, mu_per_column):
+        """side 0: every user row from the item factors; side 1: every item row from the user factors."""
+        self._chk(self._lib.yue_expo_half_sweep(self._ctx, C.c_int(side), C.c_double(lam), C.c_double(lam_y), C.c_int(1 if mu_per_column else 0)))
+
+    def expo_update_mu(self, a, b, lam_y):
+        self._chk(self._lib.yue_expo_update_mu(self._ctx, C.c_double(a), C.c_double(b), C.c_double(lam_y)))
 
     # -- UserKNN (needs no factors) ------------------------------------------------------------
     def knn_set_pairs(self, m, n, u_ptr, u_items, u_counts, i_ptr, i_users):

@@ -4,7 +4,7 @@
 //   chain_host.hip  exact sequential semantics as dataflow    scan_host.hip  predict + evalRanking's selection
 //   fism_host.hip   FISM                                      comm.hip       RCCL
 //   wrmf_host.hip   WRMF (ALS half-sweeps)                     knn_host.hip   UserKNN (neighbours, ranking)
-//   ipf_host.hip    IPF (session-graph ranking)
+//   ipf_host.hip    IPF (session-graph ranking)                expo_host.hip  ExpoMF (exposure-weighted ALS, MFMA Gram)
 #pragma once
 #include "../../include/yue_hip.h"
 
@@ -21,6 +21,7 @@
 struct ncclComm;
 struct yue_wrmf;                                     // wrmf_host.hip: pairs, schedules, workspaces of the WRMF half-sweeps
 struct yue_knn;                                      // knn_host.hip: pair lists, neighbour lists, ranking buffers of UserKNN
+struct yue_expo;                                     // expo_host.hip: mu, Gram workspace, partial sums of ExpoMF
 struct yue_ipf;                                      // ipf_host.hip: session temporal graph, weights, per-slot work arrays of IPF
 
 namespace yue_host {
@@ -191,6 +192,7 @@ struct yue_ctx {
     yue_wrmf *wrmf = nullptr;            // WRMF state (yue_wrmf_set_pairs), owned by wrmf_host.hip
     yue_knn *knn = nullptr;              // UserKNN state (yue_knn_set_pairs), owned by knn_host.hip
     yue_ipf *ipf = nullptr;              // IPF state (yue_ipf_set_graph), owned by ipf_host.hip
+    yue_expo *expo = nullptr;            // ExpoMF state (yue_expo_set_mu), owned by expo_host.hip
 };
 
 namespace yue_host {
@@ -209,6 +211,14 @@ int chain_stream(yue_ctx *c, int64_t T, double lr, double regU, double regI);
 void wrmf_release(yue_ctx *c);
 int wrmf_set_option(yue_ctx *c, const std::string &key, int64_t value);
 int wrmf_get_option(yue_ctx *c, const std::string &key, int64_t *value);
+// ... the uploaded pairs of one side (0: user rows, 1: item rows) for the other ALS solver (expo_host.hip); false when
+// yue_wrmf_set_pairs has not run for the context's current factors
+struct WrmfPairsView {
+    const int64_t *ptr, *cptr, *cbeg, *cend;
+    const int32_t *idx, *cnt, *sched, *cpos;
+    int64_t rows, n_long, chunks, n_nonempty;       // n_nonempty: rows with pairs, the first positions of sched
+};
+bool wrmf_pairs_view(const yue_ctx *c, int side, WrmfPairsView *v);
 // knn_host.hip: frees the UserKNN state; options "knn_*"
 void knn_release(yue_ctx *c);
 int knn_set_option(yue_ctx *c, const std::string &key, int64_t value);
@@ -217,4 +227,8 @@ int knn_get_option(yue_ctx *c, const std::string &key, int64_t *value);
 void ipf_release(yue_ctx *c);
 int ipf_set_option(yue_ctx *c, const std::string &key, int64_t value);
 int ipf_get_option(yue_ctx *c, const std::string &key, int64_t *value);
+// expo_host.hip: frees the ExpoMF state; options "expo_*"
+void expo_release(yue_ctx *c);
+int expo_set_option(yue_ctx *c, const std::string &key, int64_t value);
+int expo_get_option(yue_ctx *c, const std::string &key, int64_t *value);
 }  // namespace yue_host

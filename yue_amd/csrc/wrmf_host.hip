@@ -15,6 +15,7 @@ struct yue_wrmf_side {
     DevBuf<int64_t> ptr, cptr, cbeg, cend;
     DevBuf<int32_t> idx, cnt, sched, cpos;
     int64_t rows = 0, n_long = 0, chunks = 0, long_pairs = 0;
+    int64_t n_nonempty = 0;          // rows with pairs: the first n_nonempty positions of sched
 };
 
 struct yue_wrmf {
@@ -93,6 +94,8 @@ int upload_side(int64_t long_pairs, yue_wrmf_side &s, const int64_t *ptr, const 
         cptr.push_back((int64_t)cbeg.size());
         s.long_pairs += len;
     }
+    s.n_nonempty = 0;
+    for (int64_t r = 0; r < rows; ++r) s.n_nonempty += ptr[r + 1] > ptr[r] ? 1 : 0;
     s.n_long = (int64_t)cptr.size() - 1;
     s.chunks = (int64_t)cbeg.size();
     HIPCHK(s.ptr.resize((size_t)rows + 1)); HIPCHK(s.idx.resize((size_t)std::max<int64_t>(nnz, 1))); HIPCHK(s.cnt.resize((size_t)std::max<int64_t>(nnz, 1)));
@@ -116,6 +119,16 @@ int upload_side(int64_t long_pairs, yue_wrmf_side &s, const int64_t *ptr, const 
 }  // namespace
 
 namespace yue_host {
+
+bool wrmf_pairs_view(const yue_ctx *c, int side, WrmfPairsView *v) {
+    const yue_wrmf *w = c->wrmf;
+    if (!w || w->m == 0 || w->m != c->m || w->n != c->n) return false;
+    const yue_wrmf_side &s = w->side[side];
+    v->ptr = s.ptr.p; v->cptr = s.cptr.p; v->cbeg = s.cbeg.p; v->cend = s.cend.p;
+    v->idx = s.idx.p; v->cnt = s.cnt.p; v->sched = s.sched.p; v->cpos = s.cpos.p;
+    v->rows = s.rows; v->n_long = s.n_long; v->chunks = s.chunks; v->n_nonempty = s.n_nonempty;
+    return true;
+}
 
 int wrmf_set_option(yue_ctx *c, const std::string &key, int64_t value) {
     if (key == "wrmf_long_pairs") {
