@@ -312,6 +312,41 @@ int yue_expo_half_sweep(yue_ctx *ctx, int side, double lam, double lam_y, int mu
 int yue_expo_update_mu(yue_ctx *ctx, double a, double b, double lam_y);
 
 /*
+ * CoFactor (reference recommender/advanced/CoFactor.py; Liang et al., "Factorization Meets the Item Embedding") -- WRMF's ALS
+ * with the items' shifted positive PMI factorised jointly.  The factors are X = P (users), Y = Q (items) of yue_set_factors, the
+ * pairs those of yue_wrmf_set_pairs, the user sweep and the loss yue_wrmf_half_sweep(0, ...).  Needs 1 <= k <= 128.
+ *   yue_cof_cooccur      the item x item co-occurrence counts as a symmetric CSR without diagonal: count(i, j) = common users;
+ *                        items with fewer than `filter` training events (the sum of their counts) take no part, a pair is kept
+ *                        when count > filter (filter >= 0).  Posting-list counting in passes over item ranges (option
+ *                        "cof_pass_items", default 8192), integer atomics only, count then fill: exact and reproducible.  The
+ *                        CSR is bounded by option "cof_cooccur_mb" (default 1024 MiB at 8 bytes per entry): beyond it the call
+ *                        returns YUE_ERR_ARG naming the option and keeps nothing.  nnz_out: the number of entries.
+ *   yue_cof_get_cooccur  ptr[n+1], idx ascending within a row, cnt (int32), as many entries as yue_cof_cooccur reported.
+ *   yue_cof_set_sppmi    the contexts S_i of every item with their values s_ij: a symmetric CSR, rows ascending, no diagonal,
+ *                        finite values (otherwise YUE_ERR_ARG, the previous SPPMI is kept).  Builds the level schedule:
+ *                        level(i) = 1 + max(level(j): j in S_i, j < i), else 0.
+ *   yue_cof_set_state / yue_cof_get_state   the context embeddings G [n][k], the item bias w [n] and the context bias c [n], fp64.
+ *   yue_cof_item_sweep   the reference's sequential item sweep (items in id order, each reading the current rows of its
+ *                        contexts), run level by level -- the rows of a level share no context edge, so the result is that of
+ *                        the sequential sweep.  Per item i, every right-hand side before any write, contexts in ascending id:
+ *                          Y[i] = (fp32(X^T X) + sum_u alpha r x_u x_u^T + regU I + sum_j G_j G_j^T)^-1
+ *                                 (sum_u (1 + alpha r) x_u + sum_j (s_ij - w_i - c_j) G_j)                     rounded to fp32 once
+ *                          G[i] = (sum_j Y_j Y_j^T + regR I)^-1 sum_j (s_ij - w_j - c_i) Y_j   (products of Y_j Y_j^T rounded to fp32)
+ *                          w[i] = mean_j (s_ij - Y_i . G_j - c_j),   c[i] = mean_j (s_ij - Y_j . G_i - w_j)
+ *                        the last three only where S_i is not empty; an item without pairs and without contexts becomes 0.
+ *                        Both systems by an fp64 Cholesky factorisation.  A non-positive pivot returns YUE_ERR_ARG naming the
+ *                        (smallest such) row.  Bit-reproducible (no float atomics).
+ * Read-only options: "cof_last_ns" (device time of the last co-occurrence build or item sweep), "cof_last_small_ns" (of the
+ * sweep's levels of fewer than 256 rows; measured only with option "cof_level_timing" = 1, which records an event per level), "cof_levels", "cof_cooccur_nnz".
+ */
+int yue_cof_cooccur(yue_ctx *ctx, int filter, int64_t *nnz_out);
+int yue_cof_get_cooccur(yue_ctx *ctx, int64_t *ptr, int32_t *idx, int32_t *cnt);
+int yue_cof_set_sppmi(yue_ctx *ctx, const int64_t *ptr, const int32_t *idx, const double *val_f64, int64_t nnz);
+int yue_cof_set_state(yue_ctx *ctx, const double *G, const double *w, const double *c);
+int yue_cof_get_state(yue_ctx *ctx, double *G, double *w, double *c);
+int yue_cof_item_sweep(yue_ctx *ctx, double alpha, double regU, double regR);
+
+/*
  * UserKNN (reference recommender/cf/UserKNN.py) -- exact user neighbours and neighbourhood ranking.  Needs no factors.
  * A_u is the set of distinct training items of user u; sim(u, v) = 2|A_u & A_v| / |A_u | A_v| (not Jaccard: in [0, 2]).
  *   yue_knn_set_pairs  the distinct (user, item) pairs both ways: user-major (u_ptr[m+1], items ascending within a user,

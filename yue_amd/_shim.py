@@ -27,6 +27,7 @@ SYMBOLS = ['yue_last_error', 'yue_version', 'yue_ctx_create', 'yue_ctx_destroy',
            'yue_fism_set_model', 'yue_fism_get_model', 'yue_fism_epoch', 'yue_fism_rounds', 'yue_fism_scores', 'yue_fism_topn_scan',
            'yue_wrmf_set_pairs', 'yue_wrmf_half_sweep',
            'yue_expo_set_pairs', 'yue_expo_set_mu', 'yue_expo_get_mu', 'yue_expo_half_sweep', 'yue_expo_update_mu',
+           'yue_cof_cooccur', 'yue_cof_get_cooccur', 'yue_cof_set_sppmi', 'yue_cof_set_state', 'yue_cof_get_state', 'yue_cof_item_sweep',
            'yue_knn_set_pairs', 'yue_knn_neighbors', 'yue_knn_predict', 'yue_knn_topn',
            'yue_ipf_set_graph', 'yue_ipf_predict', 'yue_ipf_topn']
 
@@ -390,6 +391,45 @@ class Device(object):
 
     def expo_update_mu(self, a, b, lam_y):
         self._chk(self._lib.yue_expo_update_mu(self._ctx, C.c_double(a), C.c_double(b), C.c_double(lam_y)))
+
+    # -- CoFactor (factors: X = P, Y = Q; pairs: wrmf_set_pairs; user sweep: wrmf_half_sweep(0, ...)) ----------------
+    def cof_cooccur(self, filt):
+        """Builds the co-occurrence CSR on the device; returns (ptr int64 [n+1], idx int32 ascending, cnt int32)."""
+        nnz = C.c_int64()
+        self._chk(self._lib.yue_cof_cooccur(self._ctx, C.c_int(int(filt)), C.byref(nnz)))
+        ptr = np.empty(self.n + 1, np.int64)
+        idx = np.empty(max(nnz.value, 1), np.int32)
+        cnt = np.empty(max(nnz.value, 1), np.int32)
+        self._chk(self._lib.yue_cof_get_cooccur(self._ctx, ptr.ctypes.data_as(C.POINTER(C.c_int64)), idx.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                cnt.ctypes.data_as(C.POINTER(C.c_int32))))
+        return ptr, idx[:nnz.value], cnt[:nnz.value]
+
+    def cof_set_sppmi(self, ptr, idx, val):
+        ptr, a = _i64(ptr)
+        assert len(ptr) == self.n + 1, 'cof_set_sppmi: the pointer must hold n + 1 entries'
+        nnz = int(ptr[-1])
+        assert len(idx) == nnz and len(val) == nnz, 'cof_set_sppmi: idx and val must hold nnz entries'
+        idx, b = _i32(idx if nnz else np.zeros(1, np.int32))
+        val, c = _f64(val if nnz else np.zeros(1, np.float64))
+        self._chk(self._lib.yue_cof_set_sppmi(self._ctx, a, b, c, C.c_int64(nnz)))
+
+    def cof_set_state(self, G, w, c):
+        G, a = _f64(G)
+        w, b = _f64(w)
+        c, d = _f64(c)
+        assert G.shape == (self.n, self.k) and w.shape == (self.n,) and c.shape == (self.n,), 'cof_set_state: G [n, k], w [n], c [n]'
+        self._chk(self._lib.yue_cof_set_state(self._ctx, a, b, d))
+
+    def cof_get_state(self):
+        G = np.empty((self.n, self.k), np.float64)
+        w = np.empty(self.n, np.float64)
+        c = np.empty(self.n, np.float64)
+        self._chk(self._lib.yue_cof_get_state(self._ctx, G.ctypes.data_as(C.POINTER(C.c_double)), w.ctypes.data_as(C.POINTER(C.c_double)),
+                                              c.ctypes.data_as(C.POINTER(C.c_double))))
+        return G, w, c
+
+    def cof_item_sweep(self, alpha, regU, regR):
+        self._chk(self._lib.yue_cof_item_sweep(self._ctx, C.c_double(alpha), C.c_double(regU), C.c_double(regR)))
 
     # -- UserKNN (needs no factors) ------------------------------------------------------------
     def knn_set_pairs(self, m, n, u_ptr, u_items, u_counts, i_ptr, i_users):

@@ -1,5 +1,5 @@
-// Register-tile layout, staging and the fp64 Cholesky solve shared by the ALS solvers (WRMF: wrmf_kernels.hpp, ExpoMF:
-// expo_kernels.hpp).
+// Register-tile layout, staging, the pair sums and the fp64 Cholesky solve shared by the ALS solvers (WRMF: wrmf_kernels.hpp,
+// ExpoMF: expo_kernels.hpp, CoFactor: cof_kernels.hpp).
 //
 // A workgroup of 256 threads holds a k x k symmetric matrix (k <= 128, padded to KP = k rounded up to 4) as the 4x4 tiles of
 // its lower triangle, tile t = ta*(ta+1)/2 + tb (ta >= tb), thread `tid` owning tiles tid, tid + 256 and tid + 512 in
@@ -90,8 +90,10 @@ __device__ inline void wrmf_tile_update(double (&acc)[kWrmfTilesPerThread][4][4]
 // Factorises the k x k matrix held in the register tiles (A = L L^T, right-looking, fp64), solves A x = bvec and writes x
 // rounded to fp32 to xrow.  lds_L: k(k+1)/2 doubles (the packed factor); colraw, colL, invd, bvec: kWrmfMaxK doubles each.
 // The block must be synchronised on entry (bvec visible).  Returns false, for every thread, at a non-positive pivot.
+// Out: float (the factor rows) or double (CoFactor's context embeddings, which the reference holds in float64).
+template <typename Out>
 __device__ inline bool als_cholesky_solve(double (&acc)[kWrmfTilesPerThread][4][4], const WrmfTiles &t, int k, double *lds_L, double *colraw,
-                                          double *colL, double *invd, const double *bvec, float *xrow) {
+                                          double *colL, double *invd, const double *bvec, Out *xrow) {
     const int tid = (int)threadIdx.x;
     // right-looking Cholesky on the register tiles: column j goes out through LDS, every tile takes the rank-1 update
     for (int j = 0; j < k; ++j) {
@@ -154,10 +156,68 @@ __device__ inline bool als_cholesky_solve(double (&acc)[kWrmfTilesPerThread][4][
             if (r1 == j) v1 = x;
             else if (r1 < j) v1 = fma(-lds_L[base + r1], x, v1);
         }
-        if (r0 < k) xrow[r0] = (float)v0;
-        if (r1 < k) xrow[r1] = (float)v1;
+        if (r0 < k) xrow[r0] = (Out)v0;
+        if (r1 < k) xrow[r1] = (Out)v1;
     }
     return true;
+}
+
+// ---- the pairs of one row (WRMF's sums; CoFactor's item sweep adds its context terms to them) -----------------------------
+struct WrmfArgs {
+    const float *F;          // fixed side [nf][k]
+    int64_t nf;
+    float *X;                // solved side [nr][k] (rows written in place)
+    int64_t nr;
+    int k;
+    const int64_t *ptr;      // pairs of the solved side's rows: ptr[nr+1], idx / cnt (rows of F, counts >= 1)
+    const int32_t *idx;
+    const int32_t *cnt;
+    const int32_t *sched;    // solve order: rows longest first
+    int64_t n_long;          // the first n_long rows of sched are long: their sums come from chunk partials
+    const int64_t *cptr;     // [n_long+1] chunk range of each long row
+    const int32_t *cpos;     // per chunk: its long row's position in sched
+    const int64_t *cbeg;     // per chunk: pair range [cbeg, cend)
+    const int64_t *cend;
+    const double *G;         // fp32-rounded F^T F, slot-major [kWrmfSlots][256]
+    double *ws;              // chunk partials [chunks][kWrmfWsStride]
+    double alpha, reg;
+    int want_loss;           // side 0: sum (1 - x_old . y)^2 over the row's pairs
+    double *row_loss;        // [nr] in sched order
+    int *status;             // smallest row with a non-positive pivot (INT_MAX: none)
+};
+
+// Sums of the pairs [p0, p1) of one row: tiles (acc), b (thread t < k: bacc), and, with xo, the loss terms of the 32 rows
+// of a stage (thread 8r: row r of each stage; lacc).  Leaves the block synchronised.
+__device__ inline void wrmf_pairs(const WrmfArgs &a, const WrmfTiles &t, int64_t p0, int64_t p1, float *stage, double *sw, double *sw1,
+                                  const float *xo, double (&acc)[kWrmfTilesPerThread][4][4], double &bacc, double &lacc) {
+    const int tid = (int)threadIdx.x, k = a.k;
+    for (int64_t q0 = p0; q0 < p1; q0 += kWrmfStage) {
+        const int cnt = (int)((p1 - q0) < kWrmfStage ? (p1 - q0) : kWrmfStage);
+        __syncthreads();                                      // the previous stage has been consumed
+        wrmf_stage(a.F, k, a.idx, q0, cnt, stage);
+        if (tid < cnt) {
+            const double c = a.alpha * (double)a.cnt[q0 + tid];
+            sw[tid] = c;
+            sw1[tid] = 1.0 + c;
+        }
+        __syncthreads();
+        wrmf_tile_update(acc, t, stage, sw, cnt);
+        if (tid < k)
+            for (int j = 0; j < cnt; ++j) bacc = fma(sw1[j], (double)stage[j * kWrmfMaxK + tid], bacc);
+        if (xo) {                                              // (1 - x_old . y)^2, the dot rounded to fp32 once
+            const int r = tid >> 3, sub = tid & 7;
+            double d = 0.0;
+            for (int col = sub; col < k; col += 8) d = fma((double)xo[col], (double)stage[r * kWrmfMaxK + col], d);
+            d += __shfl_xor(d, 1);
+            d += __shfl_xor(d, 2);
+            d += __shfl_xor(d, 4);
+            if (sub == 0 && r < cnt) {
+                const double e = 1.0 - (double)(float)d;
+                lacc = fma(e, e, lacc);
+            }
+        }
+    }
+    __syncthreads();
 }
 
 }  // namespace yue

@@ -845,6 +845,7 @@ int yue_get_option(yue_ctx *c, const char *name, int64_t *value) {
     else if (key.compare(0, 4, "knn_") == 0) return yue_host::knn_get_option(c, key, value);
     else if (key.compare(0, 4, "ipf_") == 0) return yue_host::ipf_get_option(c, key, value);
     else if (key.compare(0, 5, "expo_") == 0) return yue_host::expo_get_option(c, key, value);
+    else if (key.compare(0, 4, "cof_") == 0) return yue_host::cof_get_option(c, key, value);
     else return fail(YUE_ERR_ARG, "yue_get_option: unknown option " + key);
     return YUE_OK;
 }
@@ -915,6 +916,7 @@ int yue_set_option(yue_ctx *c, const char *name, int64_t value) {
     if (key.compare(0, 4, "knn_") == 0) return yue_host::knn_set_option(c, key, value);
     if (key.compare(0, 4, "ipf_") == 0) return yue_host::ipf_set_option(c, key, value);
     if (key.compare(0, 5, "expo_") == 0) return yue_host::expo_set_option(c, key, value);
+    if (key.compare(0, 4, "cof_") == 0) return yue_host::cof_set_option(c, key, value);
     return fail(YUE_ERR_ARG, "yue_set_option: unknown option " + key);
 }
 

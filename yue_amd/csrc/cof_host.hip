@@ -1,0 +1,379 @@
+// libyue_hip.so -- CoFactor (recommender/advanced/CoFactor.py): the co-occurrence CSR and the level-scheduled item sweep
+// (include/yue_hip.h).  Kernels: cof_kernels.hpp.  The factors are the context's P (X, users) and Q (Y, items); the pairs are
+// those of yue_wrmf_set_pairs (wrmf_host.hip), whose Gram kernels the sweep reuses; the user half-sweep is yue_wrmf_half_sweep.
+#include "host_common.hpp"
+
+#include "cof_kernels.hpp"
+
+#include <climits>
+#include <numeric>
+
+using yue_host::fail;
+
+struct yue_cof {
+    // co-occurrence
+    DevBuf<int64_t> co_ptr, row_nnz, cursor;
+    DevBuf<int32_t> co_idx, co_cnt, events;
+    int64_t co_n = -1, co_nnz = 0;
+    int64_t cooccur_mb = 1024;       // bound of the co-occurrence CSR (idx + cnt: 8 bytes per entry), MiB
+    int64_t pass_items = yue::kCofRange;   // items counted per pass
+    // SPPMI and the level schedule
+    DevBuf<int64_t> sp_ptr;
+    DevBuf<int32_t> sp_idx;
+    DevBuf<double> sp_val;
+    std::vector<int64_t> h_sp_ptr;
+    std::vector<int32_t> level;      // per item
+    int64_t sp_n = -1, levels = 0;
+    // schedule of the uploaded pairs: rows by (level, pairs descending, id), the long rows' chunks
+    std::vector<int64_t> level_ptr;
+    int64_t sched_long_pairs = 0, sched_generation = -1, chunks = 0;
+    bool sched_valid = false;
+    DevBuf<int32_t> sched, lpos;
+    DevBuf<int64_t> cptr, cbeg, cend;
+    DevBuf<double> ws;
+    // state
+    DevBuf<double> G, w, c;
+    int64_t st_n = -1;
+    int st_k = 0;
+    DevBuf<int> status;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    std::vector<hipEvent_t> lev_ev;  // one in front of every level's launch and one behind the last
+    int64_t last_ns = 0, last_small_ns = 0;
+    int level_timing = 0;            // 1: time every level's launch (option cof_level_timing; tools/cofactor_bench.py)
+};
+
+namespace yue_host {
+
+void cof_release(yue_ctx *c) {
+    yue_cof *x = c->cof;
+    if (!x) return;
+    x->co_ptr.release(); x->row_nnz.release(); x->cursor.release(); x->co_idx.release(); x->co_cnt.release(); x->events.release();
+    x->sp_ptr.release(); x->sp_idx.release(); x->sp_val.release();
+    x->sched.release(); x->lpos.release(); x->cptr.release(); x->cbeg.release(); x->cend.release(); x->ws.release();
+    x->G.release(); x->w.release(); x->c.release(); x->status.release();
+    for (auto &e : x->ev) if (e) (void)hipEventDestroy(e);
+    for (auto &e : x->lev_ev) (void)hipEventDestroy(e);
+    delete x;
+    c->cof = nullptr;
+}
+
+}  // namespace yue_host
+
+namespace {
+
+int cof_state(yue_ctx *c, yue_cof **out) {
+    if (!c->cof) {
+        HIPCHK(hipSetDevice(c->device));
+        yue_cof *x = new yue_cof();
+        c->cof = x;
+        for (auto &e : x->ev) HIPCHK(hipEventCreate(&e));
+    }
+    *out = c->cof;
+    return YUE_OK;
+}
+
+template <typename T>
+int upload(DevBuf<T> &b, const std::vector<T> &h) {
+    HIPCHK(b.resize(std::max<size_t>(h.size(), 1)));
+    if (!h.empty()) HIPCHK(hipMemcpy(b.p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
+    return YUE_OK;
+}
+
+// The rows level by level (inside a level: most pairs first, ties by id) and the chunks of the rows with more than long_pairs
+// pairs; rebuilt when the pairs (a new yue_wrmf_set_pairs), the SPPMI or wrmf_long_pairs changed.
+int ensure_schedule(yue_ctx *c, yue_cof *x, const yue_host::WrmfPairsView &v, int64_t long_pairs) {
+    if (x->sched_valid && x->sched_long_pairs == long_pairs && x->sched_generation == v.generation) return YUE_OK;
+    x->sched_valid = false;
+    const int64_t n = c->n;
+    std::vector<int64_t> iptr((size_t)n + 1);
+    HIPCHK(hipMemcpy(iptr.data(), v.ptr, ((size_t)n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+    std::vector<int32_t> sched((size_t)n);
+    std::iota(sched.begin(), sched.end(), 0);
+    std::stable_sort(sched.begin(), sched.end(), [&](int32_t a, int32_t b) {
+        if (x->level[(size_t)a] != x->level[(size_t)b]) return x->level[(size_t)a] < x->level[(size_t)b];
+        return iptr[(size_t)a + 1] - iptr[(size_t)a] > iptr[(size_t)b + 1] - iptr[(size_t)b];
+    });
+    x->level_ptr.assign((size_t)x->levels + 1, 0);
+    for (int64_t i = 0; i < n; ++i) x->level_ptr[(size_t)x->level[(size_t)i] + 1]++;
+    for (int64_t l = 0; l < x->levels; ++l) x->level_ptr[(size_t)l + 1] += x->level_ptr[(size_t)l];
+    std::vector<int32_t> lpos((size_t)n, -1);
+    std::vector<int64_t> cptr(1, 0), cbeg, cend;
+    for (int64_t p = 0; p < n; ++p) {
+        const int32_t r = sched[(size_t)p];
+        const int64_t b = iptr[(size_t)r], e = iptr[(size_t)r + 1];
+        if (e - b <= long_pairs) continue;
+        lpos[(size_t)p] = (int32_t)cptr.size() - 1;
+        for (int64_t q = b; q < e; q += long_pairs) {
+            cbeg.push_back(q);
+            cend.push_back(std::min(q + long_pairs, e));
+        }
+        cptr.push_back((int64_t)cbeg.size());
+    }
+    int rc;
+    if ((rc = upload(x->sched, sched)) || (rc = upload(x->lpos, lpos)) || (rc = upload(x->cptr, cptr)) ||
+        (rc = upload(x->cbeg, cbeg)) || (rc = upload(x->cend, cend)))
+        return rc;
+    x->chunks = (int64_t)cbeg.size();
+    HIPCHK(x->ws.resize((size_t)std::max<int64_t>(x->chunks, 1) * yue::kWrmfWsStride));
+    x->sched_generation = v.generation;
+    x->sched_long_pairs = long_pairs;
+    x->sched_valid = true;
+    return YUE_OK;
+}
+
+}  // namespace
+
+namespace yue_host {
+
+int cof_set_option(yue_ctx *c, const std::string &key, int64_t value) {
+    yue_cof *x = nullptr;
+    int rc = cof_state(c, &x);
+    if (rc) return rc;
+    if (key == "cof_cooccur_mb") {
+        if (value < 1 || value > 65536) return fail(YUE_ERR_ARG, "yue_set_option: cof_cooccur_mb must be in [1, 65536]");
+        x->cooccur_mb = value;
+    } else if (key == "cof_level_timing") {
+        if (value != 0 && value != 1) return fail(YUE_ERR_ARG, "yue_set_option: cof_level_timing must be 0 or 1");
+        x->level_timing = (int)value;
+    } else if (key == "cof_pass_items") {
+        if (value < 64 || value > yue::kCofRange) return fail(YUE_ERR_ARG, "yue_set_option: cof_pass_items must be in [64, " + std::to_string(yue::kCofRange) + "]");
+        x->pass_items = value;
+    } else {
+        return fail(YUE_ERR_ARG, "yue_set_option: unknown option " + key);
+    }
+    return YUE_OK;
+}
+
+int cof_get_option(yue_ctx *c, const std::string &key, int64_t *value) {
+    const yue_cof *x = c->cof;
+    if (key == "cof_cooccur_mb") *value = x ? x->cooccur_mb : 1024;
+    else if (key == "cof_level_timing") *value = x ? x->level_timing : 0;
+    else if (key == "cof_pass_items") *value = x ? x->pass_items : yue::kCofRange;
+    else if (key == "cof_last_ns") *value = x ? x->last_ns : 0;                   // device time of the last co-occurrence build / item sweep
+    else if (key == "cof_last_small_ns") *value = x ? x->last_small_ns : 0;       // ... of the sweep's levels of fewer than 256 rows (with cof_level_timing = 1, else 0)
+    else if (key == "cof_levels") *value = x ? x->levels : 0;                     // levels of the SPPMI of yue_cof_set_sppmi
+    else if (key == "cof_cooccur_nnz") *value = x && x->co_n >= 0 ? x->co_nnz : 0;
+    else return fail(YUE_ERR_ARG, "yue_get_option: unknown option " + key);
+    return YUE_OK;
+}
+
+}  // namespace yue_host
+
+extern "C" {
+
+int yue_cof_cooccur(yue_ctx *c, int filter, int64_t *nnz_out) {
+    if (!c || !c->have_factors) return fail(YUE_ERR_ARG, "yue_cof_cooccur: call yue_set_factors first (m, n)");
+    if (filter < 0) return fail(YUE_ERR_ARG, "yue_cof_cooccur: filter must be >= 0");
+    yue_host::WrmfPairsView vu, vi;
+    if (!yue_host::wrmf_pairs_view(c, 0, &vu) || !yue_host::wrmf_pairs_view(c, 1, &vi))
+        return fail(YUE_ERR_ARG, "yue_cof_cooccur: call yue_wrmf_set_pairs first (after yue_set_factors)");
+    yue_cof *x = nullptr;
+    int rc = cof_state(c, &x);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    const int64_t n = c->n;
+    x->co_n = -1;
+    int64_t nnz_pairs = 0;
+    HIPCHK(hipMemcpy(&nnz_pairs, vi.ptr + n, sizeof(int64_t), hipMemcpyDeviceToHost));
+    HIPCHK(x->cursor.resize((size_t)std::max<int64_t>(nnz_pairs, 1)));
+    HIPCHK(x->events.resize((size_t)n));
+    HIPCHK(x->row_nnz.resize((size_t)n));
+    HIPCHK(x->co_ptr.resize((size_t)n + 1));
+    yue::CofCoArgs a{};
+    a.n = n; a.u_ptr = vu.ptr; a.u_items = vu.idx; a.i_ptr = vi.ptr; a.i_users = vi.idx; a.i_counts = vi.cnt;
+    a.cursor = x->cursor.p; a.events = x->events.p; a.filter = filter; a.range = (int)x->pass_items;
+    a.row_nnz = x->row_nnz.p; a.fill = 0;
+    HIPCHK(hipEventRecord(x->ev[0], c->stream));
+    hipLaunchKernelGGL(yue::k_cof_events, dim3((unsigned)((n + yue::kCofThreads - 1) / yue::kCofThreads)), dim3(yue::kCofThreads), 0, c->stream, a);
+    hipLaunchKernelGGL(yue::k_cof_cooccur, dim3((unsigned)n), dim3(yue::kCofThreads), 0, c->stream, a);
+    HIPCHK(hipGetLastError());
+    std::vector<int64_t> ptr((size_t)n + 1, 0);
+    HIPCHK(hipMemcpyAsync(ptr.data() + 1, x->row_nnz.p, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int64_t i = 0; i < n; ++i) ptr[(size_t)i + 1] += ptr[(size_t)i];
+    const int64_t nnz = ptr[(size_t)n];
+    if (nnz > (x->cooccur_mb << 20) / 8)
+        return fail(YUE_ERR_ARG, "yue_cof_cooccur: the co-occurrence CSR holds " + std::to_string(nnz) + " entries, more than option cof_cooccur_mb = " +
+                                     std::to_string(x->cooccur_mb) + " MiB allows (8 bytes per entry): raise cof_cooccur_mb or the filter");
+    HIPCHK(x->co_idx.resize((size_t)std::max<int64_t>(nnz, 1)));
+    HIPCHK(x->co_cnt.resize((size_t)std::max<int64_t>(nnz, 1)));
+    HIPCHK(hipMemcpyAsync(x->co_ptr.p, ptr.data(), ((size_t)n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    a.fill = 1; a.ptr = x->co_ptr.p; a.idx = x->co_idx.p; a.cnt = x->co_cnt.p;
+    hipLaunchKernelGGL(yue::k_cof_cooccur, dim3((unsigned)n), dim3(yue::kCofThreads), 0, c->stream, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(x->ev[1], c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    float ms = 0.0f;
+    HIPCHK(hipEventElapsedTime(&ms, x->ev[0], x->ev[1]));
+    x->last_ns = (int64_t)(1e6 * (double)ms);
+    x->co_n = n;
+    x->co_nnz = nnz;
+    if (nnz_out) *nnz_out = nnz;
+    return YUE_OK;
+}
+
+int yue_cof_get_cooccur(yue_ctx *c, int64_t *ptr, int32_t *idx, int32_t *cnt) {
+    if (!c || !c->cof || c->cof->co_n < 0) return fail(YUE_ERR_ARG, "yue_cof_get_cooccur: call yue_cof_cooccur first");
+    yue_cof *x = c->cof;
+    if (!ptr || (x->co_nnz > 0 && (!idx || !cnt))) return fail(YUE_ERR_ARG, "yue_cof_get_cooccur: null output array");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpy(ptr, x->co_ptr.p, ((size_t)x->co_n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (x->co_nnz > 0) {
+        HIPCHK(hipMemcpy(idx, x->co_idx.p, (size_t)x->co_nnz * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(cnt, x->co_cnt.p, (size_t)x->co_nnz * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    return YUE_OK;
+}
+
+int yue_cof_set_sppmi(yue_ctx *c, const int64_t *ptr, const int32_t *idx, const double *val, int64_t nnz) {
+    if (!c || !c->have_factors) return fail(YUE_ERR_ARG, "yue_cof_set_sppmi: call yue_set_factors first (n)");
+    if (nnz < 0 || !ptr || (nnz > 0 && (!idx || !val))) return fail(YUE_ERR_ARG, "yue_cof_set_sppmi: null array or negative nnz");
+    const int64_t n = c->n;
+    if (ptr[0] != 0 || ptr[n] != nnz) return fail(YUE_ERR_ARG, "yue_cof_set_sppmi: the pointer must run from 0 to nnz");
+    for (int64_t i = 0; i < n; ++i) {
+        if (ptr[i + 1] < ptr[i]) return fail(YUE_ERR_ARG, "yue_cof_set_sppmi: the pointer must be non-decreasing");
+        for (int64_t e = ptr[i]; e < ptr[i + 1]; ++e) {
+            if (idx[e] < 0 || idx[e] >= n) return fail(YUE_ERR_ARG, "yue_cof_set_sppmi: context id out of range in row " + std::to_string(i));
+            if (e > ptr[i] && idx[e] <= idx[e - 1]) return fail(YUE_ERR_ARG, "yue_cof_set_sppmi: row " + std::to_string(i) + " is not ascending");
+            if (idx[e] == i) return fail(YUE_ERR_ARG, "yue_cof_set_sppmi: row " + std::to_string(i) + " holds a diagonal entry");
+            if (!std::isfinite(val[e])) return fail(YUE_ERR_ARG, "yue_cof_set_sppmi: row " + std::to_string(i) + " holds a value that is not finite");
+        }
+    }
+    for (int64_t i = 0; i < n; ++i)                      // symmetric: (j, i) exists with the same value (rows ascending: binary search)
+        for (int64_t e = ptr[i]; e < ptr[i + 1]; ++e) {
+            const int32_t j = idx[e];
+            const int32_t *b = idx + ptr[j], *en = idx + ptr[j + 1];
+            const int32_t *at = std::lower_bound(b, en, (int32_t)i);
+            if (at == en || *at != (int32_t)i || val[at - idx] != val[e])
+                return fail(YUE_ERR_ARG, "yue_cof_set_sppmi: not symmetric at (" + std::to_string(i) + ", " + std::to_string(j) + ")");
+        }
+    yue_cof *x = nullptr;
+    int rc = cof_state(c, &x);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    x->sp_n = -1;
+    x->sched_valid = false;
+    HIPCHK(x->sp_ptr.resize((size_t)n + 1));
+    HIPCHK(x->sp_idx.resize((size_t)std::max<int64_t>(nnz, 1)));
+    HIPCHK(x->sp_val.resize((size_t)std::max<int64_t>(nnz, 1)));
+    HIPCHK(hipMemcpy(x->sp_ptr.p, ptr, ((size_t)n + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+    if (nnz > 0) {
+        HIPCHK(hipMemcpy(x->sp_idx.p, idx, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(x->sp_val.p, val, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice));
+    }
+    // level(i) = 1 + max level of the contexts with a smaller id (those the sequential sweep has updated before it reaches i)
+    x->level.assign((size_t)n, 0);
+    int32_t top = -1;
+    for (int64_t i = 0; i < n; ++i) {
+        int32_t l = 0;
+        for (int64_t e = ptr[i]; e < ptr[i + 1] && idx[e] < i; ++e) l = std::max(l, x->level[(size_t)idx[e]] + 1);
+        x->level[(size_t)i] = l;
+        top = std::max(top, l);
+    }
+    x->levels = (int64_t)top + 1;
+    x->h_sp_ptr.assign(ptr, ptr + n + 1);
+    x->sp_n = n;
+    return YUE_OK;
+}
+
+int yue_cof_set_state(yue_ctx *c, const double *G, const double *w, const double *cb) {
+    if (!c || !c->have_factors) return fail(YUE_ERR_ARG, "yue_cof_set_state: call yue_set_factors first (n, k)");
+    if (!G || !w || !cb) return fail(YUE_ERR_ARG, "yue_cof_set_state: null array");
+    yue_cof *x = nullptr;
+    int rc = cof_state(c, &x);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const size_t n = (size_t)c->n, k = (size_t)c->k;
+    x->st_n = -1;
+    HIPCHK(x->G.resize(std::max<size_t>(n * k, 1))); HIPCHK(x->w.resize(std::max<size_t>(n, 1))); HIPCHK(x->c.resize(std::max<size_t>(n, 1)));
+    HIPCHK(hipMemcpy(x->G.p, G, n * k * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(x->w.p, w, n * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(x->c.p, cb, n * sizeof(double), hipMemcpyHostToDevice));
+    x->st_n = c->n;
+    x->st_k = c->k;
+    return YUE_OK;
+}
+
+int yue_cof_get_state(yue_ctx *c, double *G, double *w, double *cb) {
+    if (!c || !c->cof || c->cof->st_n < 0) return fail(YUE_ERR_ARG, "yue_cof_get_state: call yue_cof_set_state first");
+    if (!G || !w || !cb) return fail(YUE_ERR_ARG, "yue_cof_get_state: null array");
+    yue_cof *x = c->cof;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const size_t n = (size_t)x->st_n, k = (size_t)x->st_k;
+    HIPCHK(hipMemcpy(G, x->G.p, n * k * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(w, x->w.p, n * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(cb, x->c.p, n * sizeof(double), hipMemcpyDeviceToHost));
+    return YUE_OK;
+}
+
+int yue_cof_item_sweep(yue_ctx *c, double alpha, double regU, double regR) {
+    if (!c || !c->have_factors) return fail(YUE_ERR_ARG, "yue_cof_item_sweep: no factors uploaded");
+    if (c->k > yue::kWrmfMaxK)
+        return fail(YUE_ERR_ARG, "yue_cof_item_sweep: k = " + std::to_string(c->k) + " is not supported (CoFactor solves need 1 <= k <= 128)");
+    if (!std::isfinite(alpha) || !std::isfinite(regU) || !std::isfinite(regR) || alpha < 0)
+        return fail(YUE_ERR_ARG, "yue_cof_item_sweep: alpha, regU and regR must be finite, alpha >= 0");
+    yue_host::WrmfPairsView v;
+    if (!yue_host::wrmf_pairs_view(c, 1, &v)) return fail(YUE_ERR_ARG, "yue_cof_item_sweep: call yue_wrmf_set_pairs first (after yue_set_factors)");
+    yue_cof *x = c->cof;
+    if (!x || x->sp_n != c->n) return fail(YUE_ERR_ARG, "yue_cof_item_sweep: call yue_cof_set_sppmi first (after yue_set_factors)");
+    if (x->st_n != c->n || x->st_k != c->k) return fail(YUE_ERR_ARG, "yue_cof_item_sweep: call yue_cof_set_state first (G, w, c for the current n and k)");
+    HIPCHK(hipSetDevice(c->device));
+    int64_t long_pairs = 0;
+    int rc = yue_host::wrmf_get_option(c, "wrmf_long_pairs", &long_pairs);
+    if (rc || (rc = ensure_schedule(c, x, v, long_pairs))) return rc;
+    const int k = c->k;
+    yue::CofArgs a{};
+    a.w.F = c->P.p; a.w.nf = c->m; a.w.X = c->Q.p; a.w.nr = c->n; a.w.k = k;
+    a.w.ptr = v.ptr; a.w.idx = v.idx; a.w.cnt = v.cnt; a.w.sched = x->sched.p;
+    a.w.cptr = x->cptr.p; a.w.cbeg = x->cbeg.p; a.w.cend = x->cend.p; a.w.ws = x->ws.p;
+    a.w.alpha = alpha; a.w.reg = regU; a.w.want_loss = 0;
+    a.lpos = x->lpos.p;
+    a.sp_ptr = x->sp_ptr.p; a.sp_idx = x->sp_idx.p; a.sp_val = x->sp_val.p;
+    a.G = x->G.p; a.wb = x->w.p; a.cb = x->c.p; a.regR = regR;
+    HIPCHK(x->status.resize(1));
+    a.w.status = x->status.p;
+    const int none = INT_MAX;
+    HIPCHK(hipMemcpyAsync(x->status.p, &none, sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipEventRecord(x->ev[0], c->stream));
+    if ((rc = yue_host::wrmf_gram(c, 1, &a.w.G))) return rc;           // X^T X, rounded to fp32 once
+    if (x->chunks > 0) hipLaunchKernelGGL(yue::k_cof_chunk, dim3((unsigned)x->chunks), dim3(yue::kWrmfThreads), 0, c->stream, a);
+    const int lds = yue::wrmf_dyn_lds(k);
+    HIPCHK(hipFuncSetAttribute((const void *)yue::k_cof_solve, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    const bool timed = x->level_timing != 0;
+    while (timed && (int64_t)x->lev_ev.size() < x->levels + 1) {
+        hipEvent_t e;
+        HIPCHK(hipEventCreate(&e));
+        x->lev_ev.push_back(e);
+    }
+    for (int64_t l = 0; l < x->levels; ++l) {                          // one launch per level: the stream orders the levels
+        const int64_t rows = x->level_ptr[(size_t)l + 1] - x->level_ptr[(size_t)l];
+        a.pos0 = x->level_ptr[(size_t)l];
+        if (timed) HIPCHK(hipEventRecord(x->lev_ev[(size_t)l], c->stream));
+        hipLaunchKernelGGL(yue::k_cof_solve, dim3((unsigned)rows), dim3(yue::kWrmfThreads), lds, c->stream, a);
+    }
+    if (timed) HIPCHK(hipEventRecord(x->lev_ev[(size_t)x->levels], c->stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(x->ev[1], c->stream));
+    int status = INT_MAX;
+    HIPCHK(hipMemcpyAsync(&status, x->status.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    float ms = 0.0f;
+    HIPCHK(hipEventElapsedTime(&ms, x->ev[0], x->ev[1]));
+    x->last_ns = (int64_t)(1e6 * (double)ms);
+    double small_ms = 0.0;
+    for (int64_t l = 0; timed && l < x->levels; ++l)
+        if (x->level_ptr[(size_t)l + 1] - x->level_ptr[(size_t)l] < 256) {
+            HIPCHK(hipEventElapsedTime(&ms, x->lev_ev[(size_t)l], x->lev_ev[(size_t)l + 1]));
+            small_ms += (double)ms;
+        }
+    x->last_small_ns = (int64_t)(1e6 * small_ms);
+    if (status != INT_MAX)
+        return fail(YUE_ERR_ARG, "yue_cof_item_sweep: non-positive pivot in a Cholesky factorisation of item row " + std::to_string(status) +
+                                     " (raise regU or regR)");
+    return YUE_OK;
+}
+
+}  // extern "C"

@@ -5,6 +5,7 @@
 //   fism_host.hip   FISM                                      comm.hip       RCCL
 //   wrmf_host.hip   WRMF (ALS half-sweeps)                     knn_host.hip   UserKNN (neighbours, ranking)
 //   ipf_host.hip    IPF (session-graph ranking)                expo_host.hip  ExpoMF (exposure-weighted ALS, MFMA Gram)
+//   cof_host.hip    CoFactor (co-occurrence, level-scheduled item sweep)
 #pragma once
 #include "../../include/yue_hip.h"
 
@@ -22,6 +23,7 @@ struct ncclComm;
 struct yue_wrmf;                                     // wrmf_host.hip: pairs, schedules, workspaces of the WRMF half-sweeps
 struct yue_knn;                                      // knn_host.hip: pair lists, neighbour lists, ranking buffers of UserKNN
 struct yue_expo;                                     // expo_host.hip: mu, Gram workspace, partial sums of ExpoMF
+struct yue_cof;                                      // cof_host.hip: co-occurrence CSR, SPPMI, level schedule, G / w / c of CoFactor
 struct yue_ipf;                                      // ipf_host.hip: session temporal graph, weights, per-slot work arrays of IPF
 
 namespace yue_host {
@@ -193,6 +195,7 @@ struct yue_ctx {
     yue_knn *knn = nullptr;              // UserKNN state (yue_knn_set_pairs), owned by knn_host.hip
     yue_ipf *ipf = nullptr;              // IPF state (yue_ipf_set_graph), owned by ipf_host.hip
     yue_expo *expo = nullptr;            // ExpoMF state (yue_expo_set_mu), owned by expo_host.hip
+    yue_cof *cof = nullptr;              // CoFactor state (yue_cof_*), owned by cof_host.hip
 };
 
 namespace yue_host {
@@ -217,8 +220,12 @@ struct WrmfPairsView {
     const int64_t *ptr, *cptr, *cbeg, *cend;
     const int32_t *idx, *cnt, *sched, *cpos;
     int64_t rows, n_long, chunks, n_nonempty;       // n_nonempty: rows with pairs, the first positions of sched
+    int64_t generation;                             // counts the uploads of yue_wrmf_set_pairs
 };
 bool wrmf_pairs_view(const yue_ctx *c, int side, WrmfPairsView *v);
+// ... and the fp32-rounded F^T F of the side's fixed factors (0: Y^T Y, 1: X^T X), queued on the context's stream into the
+// WRMF state's slot-major buffer (cof_host.hip)
+int wrmf_gram(yue_ctx *c, int side, const double **G);
 // knn_host.hip: frees the UserKNN state; options "knn_*"
 void knn_release(yue_ctx *c);
 int knn_set_option(yue_ctx *c, const std::string &key, int64_t value);
@@ -231,4 +238,8 @@ int ipf_get_option(yue_ctx *c, const std::string &key, int64_t *value);
 void expo_release(yue_ctx *c);
 int expo_set_option(yue_ctx *c, const std::string &key, int64_t value);
 int expo_get_option(yue_ctx *c, const std::string &key, int64_t *value);
+// cof_host.hip: frees the CoFactor state; options "cof_*"
+void cof_release(yue_ctx *c);
+int cof_set_option(yue_ctx *c, const std::string &key, int64_t value);
+int cof_get_option(yue_ctx *c, const std::string &key, int64_t *value);
 }  // namespace yue_host

@@ -20,6 +20,7 @@ struct yue_wrmf_side {
 
 struct yue_wrmf {
     int64_t m = 0, n = 0, nnz = 0;
+    int64_t generation = 0;          // bumped by every yue_wrmf_set_pairs: lets a dependent schedule (cof_host.hip) see a new upload
     yue_wrmf_side side[2];
     DevBuf<double> gram_part, G, ws, row_loss, loss;
     DevBuf<int> status;
@@ -127,7 +128,21 @@ bool wrmf_pairs_view(const yue_ctx *c, int side, WrmfPairsView *v) {
     v->ptr = s.ptr.p; v->cptr = s.cptr.p; v->cbeg = s.cbeg.p; v->cend = s.cend.p;
     v->idx = s.idx.p; v->cnt = s.cnt.p; v->sched = s.sched.p; v->cpos = s.cpos.p;
     v->rows = s.rows; v->n_long = s.n_long; v->chunks = s.chunks; v->n_nonempty = s.n_nonempty;
+    v->generation = w->generation;
     return true;
+}
+
+int wrmf_gram(yue_ctx *c, int side, const double **G) {
+    yue_wrmf *w = c->wrmf;
+    if (!w || w->m == 0 || w->m != c->m || w->n != c->n) return fail(YUE_ERR_ARG, "wrmf_gram: call yue_wrmf_set_pairs first");
+    const float *F = side == 0 ? c->Q.p : c->P.p;
+    const int64_t nf = side == 0 ? c->n : c->m;
+    const int64_t rpb = (nf + yue::kWrmfGramBlocks - 1) / yue::kWrmfGramBlocks;
+    hipLaunchKernelGGL(yue::k_wrmf_gram_part, dim3(yue::kWrmfGramBlocks), dim3(yue::kWrmfThreads), 0, c->stream, F, nf, c->k, rpb, w->gram_part.p);
+    hipLaunchKernelGGL(yue::k_wrmf_gram_sum, dim3(yue::kWrmfSlots), dim3(yue::kWrmfThreads), 0, c->stream, (const double *)w->gram_part.p, yue::kWrmfGramBlocks, w->G.p);
+    HIPCHK(hipGetLastError());
+    *G = w->G.p;
+    return YUE_OK;
 }
 
 int wrmf_set_option(yue_ctx *c, const std::string &key, int64_t value) {
@@ -188,6 +203,7 @@ int yue_wrmf_set_pairs(yue_ctx *c, const int64_t *u_ptr, const int32_t *u_items,
     HIPCHK(w->loss.resize(1));
     HIPCHK(w->status.resize(1));
     w->m = m; w->n = n; w->nnz = nnz;
+    w->generation++;
     return YUE_OK;
 }
 
@@ -209,15 +225,13 @@ int yue_wrmf_half_sweep(yue_ctx *c, int side, double alpha, double reg, double *
     a.X = side == 0 ? c->P.p : c->Q.p; a.nr = s.rows; a.k = k;
     a.ptr = s.ptr.p; a.idx = s.idx.p; a.cnt = s.cnt.p; a.sched = s.sched.p;
     a.n_long = s.n_long; a.cptr = s.cptr.p; a.cpos = s.cpos.p; a.cbeg = s.cbeg.p; a.cend = s.cend.p;
-    a.G = w->G.p; a.ws = w->ws.p; a.alpha = alpha; a.reg = reg;
+    a.ws = w->ws.p; a.alpha = alpha; a.reg = reg;
     a.want_loss = side == 0 ? 1 : 0; a.row_loss = w->row_loss.p; a.status = w->status.p;
     const int none = INT_MAX;
     HIPCHK(hipMemcpyAsync(w->status.p, &none, sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipEventRecord(w->ev[0], c->stream));
-    // F^T F of the fixed side, rounded to fp32 once
-    const int64_t rpb = (nf + yue::kWrmfGramBlocks - 1) / yue::kWrmfGramBlocks;
-    hipLaunchKernelGGL(yue::k_wrmf_gram_part, dim3(yue::kWrmfGramBlocks), dim3(yue::kWrmfThreads), 0, c->stream, a.F, nf, k, rpb, w->gram_part.p);
-    hipLaunchKernelGGL(yue::k_wrmf_gram_sum, dim3(yue::kWrmfSlots), dim3(yue::kWrmfThreads), 0, c->stream, (const double *)w->gram_part.p, yue::kWrmfGramBlocks, w->G.p);
+    int rc = yue_host::wrmf_gram(c, side, &a.G);                // F^T F of the fixed side, rounded to fp32 once
+    if (rc) return rc;
     HIPCHK(hipEventRecord(w->ev[1], c->stream));
     if (s.chunks > 0) hipLaunchKernelGGL(yue::k_wrmf_chunk, dim3((unsigned)s.chunks), dim3(yue::kWrmfThreads), 0, c->stream, a);
     HIPCHK(hipEventRecord(w->ev[2], c->stream));

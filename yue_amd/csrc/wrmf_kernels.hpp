@@ -16,63 +16,6 @@
 
 namespace yue {
 
-struct WrmfArgs {
-    const float *F;          // fixed side [nf][k]
-    int64_t nf;
-    float *X;                // solved side [nr][k] (rows written in place)
-    int64_t nr;
-    int k;
-    const int64_t *ptr;      // pairs of the solved side's rows: ptr[nr+1], idx / cnt (rows of F, counts >= 1)
-    const int32_t *idx;
-    const int32_t *cnt;
-    const int32_t *sched;    // solve order: rows longest first
-    int64_t n_long;          // the first n_long rows of sched are long: their sums come from chunk partials
-    const int64_t *cptr;     // [n_long+1] chunk range of each long row
-    const int32_t *cpos;     // per chunk: its long row's position in sched
-    const int64_t *cbeg;     // per chunk: pair range [cbeg, cend)
-    const int64_t *cend;
-    const double *G;         // fp32-rounded F^T F, slot-major [kWrmfSlots][256]
-    double *ws;              // chunk partials [chunks][kWrmfWsStride]
-    double alpha, reg;
-    int want_loss;           // side 0: sum (1 - x_old . y)^2 over the row's pairs
-    double *row_loss;        // [nr] in sched order
-    int *status;             // smallest row with a non-positive pivot (INT_MAX: none)
-};
-
-// Sums of the pairs [p0, p1) of one row: tiles (acc), b (thread t < k: bacc), and, with xo, the loss terms of the 32 rows
-// of a stage (thread 8r: row r of each stage; lacc).  Leaves the block synchronised.
-__device__ inline void wrmf_pairs(const WrmfArgs &a, const WrmfTiles &t, int64_t p0, int64_t p1, float *stage, double *sw, double *sw1,
-                                  const float *xo, double (&acc)[kWrmfTilesPerThread][4][4], double &bacc, double &lacc) {
-    const int tid = (int)threadIdx.x, k = a.k;
-    for (int64_t q0 = p0; q0 < p1; q0 += kWrmfStage) {
-        const int cnt = (int)((p1 - q0) < kWrmfStage ? (p1 - q0) : kWrmfStage);
-        __syncthreads();                                      // the previous stage has been consumed
-        wrmf_stage(a.F, k, a.idx, q0, cnt, stage);
-        if (tid < cnt) {
-            const double c = a.alpha * (double)a.cnt[q0 + tid];
-            sw[tid] = c;
-            sw1[tid] = 1.0 + c;
-        }
-        __syncthreads();
-        wrmf_tile_update(acc, t, stage, sw, cnt);
-        if (tid < k)
-            for (int j = 0; j < cnt; ++j) bacc = fma(sw1[j], (double)stage[j * kWrmfMaxK + tid], bacc);
-        if (xo) {                                              // (1 - x_old . y)^2, the dot rounded to fp32 once
-            const int r = tid >> 3, sub = tid & 7;
-            double d = 0.0;
-            for (int col = sub; col < k; col += 8) d = fma((double)xo[col], (double)stage[r * kWrmfMaxK + col], d);
-            d += __shfl_xor(d, 1);
-            d += __shfl_xor(d, 2);
-            d += __shfl_xor(d, 4);
-            if (sub == 0 && r < cnt) {
-                const double e = 1.0 - (double)(float)d;
-                lacc = fma(e, e, lacc);
-            }
-        }
-    }
-    __syncthreads();
-}
-
 // ---- F^T F: block partials over fixed row ranges, then one fixed-order sum rounded to fp32 ------------------------
 __global__ __launch_bounds__(kWrmfThreads) void k_wrmf_gram_part(const float *__restrict__ F, int64_t nf, int k, int64_t rows_per_block, double *__restrict__ part) {
     __shared__ __attribute__((aligned(16))) float stage[kWrmfStage * kWrmfMaxK];

@@ -4,7 +4,7 @@ import time
 from .tool.config import Config
 from .yue import Yue
 
-MENU = {'1': 'BPR', '2': 'FISM', '3': 'WRMF', '4': 'IPF', '5': 'UserKNN', 'a1': 'CUNE', 'a6': 'ExpoMF'}
+MENU = {'1': 'BPR', '2': 'FISM', '3': 'WRMF', '4': 'IPF', '5': 'UserKNN', 'a1': 'CUNE', 'a6': 'ExpoMF', 'a7': 'CoFactor'}
 
 
 def main():
@@ -15,7 +15,7 @@ def main():
     print('1. BPR   2. FISM   3. WRMF   4. IPF   5. UserKNN')
     print('Advanced Recommenders:')
     print('a1. CUNE (training loop; needs -friends, see recommender/advanced/CUNE.py)')
-    print('a6. ExpoMF')
+    print('a6. ExpoMF   a7. CoFactor')
     print('=' * 80)
     order = input('Please enter the num of the algorithm to run it:')
     start = time.time()
