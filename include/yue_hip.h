@@ -303,6 +303,13 @@ int yue_wrmf_half_sweep(yue_ctx *ctx, int side, double alpha, double reg, double
  *                        theta, beta and mu (per item); the sums in fp64, mu rounded to fp32 once.
  * Read-only options: "expo_last_ns" / "expo_last_gram_ns" (device time of the last half-sweep or mu update / of its dense
  * Gram launches), "expo_last_batches".
+ *   yue_expo_gram_rows   diagnostic, like those options: the dense stage of a half-sweep alone, for the tests.  For each of the
+ *                        nrows listed rows r of the side (any order, repeats allowed) the packed lower triangle
+ *                        out[t][p(p+1)/2 + q] (p >= q) of sum over ALL columns j of A~_j f_j f_j^T, A~ the posterior WITHOUT the
+ *                        A = 1 overwrite on the pairs, no lam*I.  Runs the half-sweep's own Gram kernel with the pair-block
+ *                        shape and the column splits of a half-sweep over all the side's rows; the list takes the place of the
+ *                        schedule and the splits are summed in order in fp64, as the solve sums them.  Refuses what the
+ *                        half-sweep refuses, and a list whose Grams exceed "expo_gram_mb".  Changes no factor.
  */
 int yue_expo_set_pairs(yue_ctx *ctx, const int64_t *u_ptr, const int32_t *u_items, const int32_t *u_counts,
                        const int64_t *i_ptr, const int32_t *i_users, const int32_t *i_counts, int64_t nnz);
@@ -310,6 +317,7 @@ int yue_expo_set_mu(yue_ctx *ctx, const float *mu, int64_t n);
 int yue_expo_get_mu(yue_ctx *ctx, float *mu, int64_t n);
 int yue_expo_half_sweep(yue_ctx *ctx, int side, double lam, double lam_y, int mu_per_column);
 int yue_expo_update_mu(yue_ctx *ctx, double a, double b, double lam_y);
+int yue_expo_gram_rows(yue_ctx *ctx, int side, int mu_per_column, double lam_y, const int32_t *rows, int64_t nrows, double *out);
 
 /*
  * CoFactor (reference recommender/advanced/CoFactor.py; Liang et al., "Factorization Meets the Item Embedding") -- WRMF's ALS

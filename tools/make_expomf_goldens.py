@@ -22,6 +22,12 @@ expomf_s_k20 must come out stable for every user, or the tool fails.
 g13_expomf_c2rows: C2 (100,000 x 50,000, 50 events per user, the shape of bench.py --workload c2) with seeded factors at
 k = 64: the reference's a_row_batch + _solve on 256 sampled users and 256 sampled items; the inputs are regenerated from the
 seeds by tests/helpers/numpy_expomf.py: c2_inputs.
+
+g13_expomf_trained.json: no reference run, settings and recorded results only.  The cases of tests/test_gpu_expomf_stages.py
+(numpy_expomf.TRAINED: seeded inputs at trained scale, regenerated from the seeds by the tests) with e_ref per case and per
+output: the reference's arithmetic (numpy_expomf.expo_reference_rows / _gram / _mu, pinned to the reference's class by
+tests/test_expomf_golden.py and tests/test_expomf_power.py) against the fp64 contract on the same inputs.  The tool fails if
+any e_ref exceeds 1e-5: a badly conditioned shape must be reshaped, not given a loose bound.
 """
 import json
 import os
@@ -203,6 +209,26 @@ def c2rows():
     print('c2rows: e_ref theta %.2e beta %.2e; reference %.3f s per user row, %.3f s per item row' % (e['theta'], e['beta'], s_user, s_item))
 
 
+E_REF_CAP = 1e-5
+
+
+def trained():
+    out = {'rule': 'device vs contract <= max(4 * e_ref, 1e-6); e_ref = reference arithmetic vs fp64 contract on the same inputs',
+           'e_ref_cap': E_REF_CAP, 'cases': {}}
+    for tag, c in ne.TRAINED.items():
+        e = ne.trained_e_ref(tag)
+        out['cases'][tag] = dict(c, e_ref=e)
+        print('%-9s m=%d n=%d k=%d: ' % (tag, c['m'], c['n'], c['k']) + ' '.join('%s %.2e' % kv for kv in sorted(e.items())), flush=True)
+    inp = ne.c2_trained()
+    users, items = ne.c2_sample(ne.C2_TRAINED_SEED, inp['user_major'][0], inp['item_major'][0])
+    e = ne.c2_trained_e_ref(inp, users, items)
+    out['c2'] = {'seed': ne.C2_TRAINED_SEED, 'shape': [inp['m'], inp['n'], 50, inp['k']], 'rows': [len(users), len(items)], 'e_ref': e}
+    print('c2        ' + ' '.join('%s %.2e' % kv for kv in sorted(e.items())), flush=True)
+    worst = max(max(c['e_ref'].values()) for c in list(out['cases'].values()) + [out['c2']])
+    assert worst <= E_REF_CAP, 'an e_ref of %.2e exceeds the cap %.0e: reshape that case' % (worst, E_REF_CAP)
+    json.dump(out, open(os.path.join(mg.OUT, 'g13_expomf_trained.json'), 'w'), indent=1)
+
+
 def equalise(m0, n0, d):
     """Lines that make the number of users equal the number of tracks: test-only users (one late event each on track t0)."""
     tracks = set(r[2] for r in mg.synth.text_events(m0, n0, d))
@@ -227,6 +253,8 @@ def main():
             case(tmp, tag, ds, extra, k, 2, topn='3' if tag == 'expomf_s_k20' else '5,10', must_be_stable=tag == 'expomf_s_k20')
     if not only or 'c2rows' in only:
         c2rows()
+    if not only or 'trained' in only:
+        trained()
 
 
 if __name__ == '__main__':

@@ -26,7 +26,7 @@ SYMBOLS = ['yue_last_error', 'yue_version', 'yue_ctx_create', 'yue_ctx_destroy',
            'yue_default_round_events', 'yue_epoch_plan',
            'yue_fism_set_model', 'yue_fism_get_model', 'yue_fism_epoch', 'yue_fism_rounds', 'yue_fism_scores', 'yue_fism_topn_scan',
            'yue_wrmf_set_pairs', 'yue_wrmf_half_sweep',
-           'yue_expo_set_pairs', 'yue_expo_set_mu', 'yue_expo_get_mu', 'yue_expo_half_sweep', 'yue_expo_update_mu',
+           'yue_expo_set_pairs', 'yue_expo_set_mu', 'yue_expo_get_mu', 'yue_expo_half_sweep', 'yue_expo_update_mu', 'yue_expo_gram_rows',
            'yue_cof_cooccur', 'yue_cof_get_cooccur', 'yue_cof_set_sppmi', 'yue_cof_set_state', 'yue_cof_get_state', 'yue_cof_item_sweep',
            'yue_knn_set_pairs', 'yue_knn_neighbors', 'yue_knn_predict', 'yue_knn_topn',
            'yue_ipf_set_graph', 'yue_ipf_predict', 'yue_ipf_topn']
@@ -391,6 +391,15 @@ class Device(object):
 
     def expo_update_mu(self, a, b, lam_y):
         self._chk(self._lib.yue_expo_update_mu(self._ctx, C.c_double(a), C.c_double(b), C.c_double(lam_y)))
+
+    def expo_gram_rows(self, side, mu_per_column, lam_y, rows):
+        """Diagnostic: the dense stage of a half-sweep alone.  fp64 [len(rows), k(k+1)/2]: per listed row the packed lower
+        triangle of sum over all columns of A~ f f^T (no A = 1 on the pairs, no lam*I), from the half-sweep's own Gram kernel."""
+        rows, p = _i32(rows)
+        out = np.empty((len(rows), self.k * (self.k + 1) // 2), np.float64)
+        self._chk(self._lib.yue_expo_gram_rows(self._ctx, C.c_int(side), C.c_int(1 if mu_per_column else 0), C.c_double(lam_y), p,
+                                               C.c_int64(len(rows)), out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
 
     # -- CoFactor (factors: X = P, Y = Q; pairs: wrmf_set_pairs; user sweep: wrmf_half_sweep(0, ...)) ----------------
     def cof_cooccur(self, filt):

@@ -12,7 +12,7 @@ using yue_host::fail;
 struct yue_expo {
     DevBuf<float> mu, gws;
     DevBuf<double> ws, part;
-    DevBuf<int> status;
+    DevBuf<int> status, rows;        // rows: the caller's list of yue_expo_gram_rows
     int64_t n_mu = 0;
     hipEvent_t ev[2] = {nullptr, nullptr};
     std::vector<std::pair<hipEvent_t, hipEvent_t>> gram_ev;     // brackets of the Gram launches of the last half-sweep
@@ -25,7 +25,7 @@ namespace yue_host {
 void expo_release(yue_ctx *c) {
     yue_expo *x = c->expo;
     if (!x) return;
-    x->mu.release(); x->gws.release(); x->ws.release(); x->part.release(); x->status.release();
+    x->mu.release(); x->gws.release(); x->ws.release(); x->part.release(); x->status.release(); x->rows.release();
     for (auto &e : x->ev) if (e) (void)hipEventDestroy(e);
     for (auto &p : x->gram_ev) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
     delete x;
@@ -57,10 +57,40 @@ int splits_for(int64_t groups, int64_t cols, int64_t *cols_per_split) {
     return (int)((chunks + per - 1) / per);
 }
 
+// shapes of the dense Gram for a side of `rows` rows against nf columns: pair blocks of 32 over gy groups of four waves with nb
+// blocks each, column splits.  One place for yue_expo_half_sweep and yue_expo_gram_rows.
+struct GramPlan { int npairs, gy, nb, splits; int64_t cols_per_split, tiles_all; };
+GramPlan gram_plan(int k, int64_t rows, int64_t nf) {
+    GramPlan g{};
+    g.npairs = k * (k + 1) / 2;
+    const int nblk = (g.npairs + 31) / 32;
+    g.gy = (nblk + 23) / 24;                                         // at most 6 blocks per wave: 96 + 96 accumulator registers
+    const int need = (nblk + 4 * g.gy - 1) / (4 * g.gy);
+    g.nb = need <= 2 ? 2 : need <= 4 ? 4 : 6;
+    g.tiles_all = (rows + yue::kExpoTile - 1) / yue::kExpoTile;
+    g.splits = splits_for(g.tiles_all * g.gy, nf, &g.cols_per_split);
+    return g;
+}
+
 template <int NB>
 int launch_gram(const yue::ExpoArgs &a, dim3 grid, int lds, hipStream_t st) {
     HIPCHK(hipFuncSetAttribute((const void *)yue::k_expo_gram<NB>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     hipLaunchKernelGGL(yue::k_expo_gram<NB>, grid, dim3(256), lds, st, a);
+    return YUE_OK;
+}
+
+int launch_gram_nb(int nb, const yue::ExpoArgs &a, dim3 grid, int lds, hipStream_t st) {
+    return nb == 2 ? launch_gram<2>(a, grid, lds, st) : nb == 4 ? launch_gram<4>(a, grid, lds, st) : launch_gram<6>(a, grid, lds, st);
+}
+
+// what a half-sweep and the Gram read-out refuse alike
+int side_checks(yue_ctx *c, const std::string &who, int side, int mu_per_column) {
+    if (side != 0 && side != 1) return fail(YUE_ERR_ARG, who + ": side must be 0 (user rows) or 1 (item rows)");
+    if (mu_per_column != 0 && mu_per_column != 1) return fail(YUE_ERR_ARG, who + ": mu_per_column must be 0 or 1");
+    // mu holds one value per item: the columns of the user side are items; those of the item side are users, which mu can
+    // index only when m == n (the reference's own rule for that case)
+    if (side == 0 && !mu_per_column) return fail(YUE_ERR_ARG, who + ": the user side takes mu per column (per item)");
+    if (side == 1 && mu_per_column && c->m != c->n) return fail(YUE_ERR_ARG, who + ": mu per column on the item side needs m == n");
     return YUE_OK;
 }
 
@@ -138,13 +168,8 @@ int yue_expo_half_sweep(yue_ctx *c, int side, double lam, double lam_y, int mu_p
     yue_expo *x = nullptr;
     int rc = common_checks(c, "yue_expo_half_sweep", &x, lam_y);
     if (rc) return rc;
-    if (side != 0 && side != 1) return fail(YUE_ERR_ARG, "yue_expo_half_sweep: side must be 0 (user rows) or 1 (item rows)");
+    if ((rc = side_checks(c, "yue_expo_half_sweep", side, mu_per_column))) return rc;
     if (!std::isfinite(lam) || lam < 0) return fail(YUE_ERR_ARG, "yue_expo_half_sweep: lam must be finite and >= 0");
-    if (mu_per_column != 0 && mu_per_column != 1) return fail(YUE_ERR_ARG, "yue_expo_half_sweep: mu_per_column must be 0 or 1");
-    // mu holds one value per item: the columns of the user side are items; those of the item side are users, which mu can
-    // index only when m == n (the reference's own rule for that case)
-    if (side == 0 && !mu_per_column) return fail(YUE_ERR_ARG, "yue_expo_half_sweep: the user side takes mu per column (per item)");
-    if (side == 1 && mu_per_column && c->m != c->n) return fail(YUE_ERR_ARG, "yue_expo_half_sweep: mu per column on the item side needs m == n");
     yue_host::WrmfPairsView v;
     if (!yue_host::wrmf_pairs_view(c, side, &v)) return fail(YUE_ERR_ARG, "yue_expo_half_sweep: call yue_expo_set_pairs first (after yue_set_factors)");
     HIPCHK(hipSetDevice(c->device));
@@ -155,15 +180,11 @@ int yue_expo_half_sweep(yue_ctx *c, int side, double lam, double lam_y, int mu_p
     a.ptr = v.ptr; a.idx = v.idx; a.cnt = v.cnt; a.sched = v.sched;
     a.n_long = v.n_long; a.cptr = v.cptr; a.cpos = v.cpos; a.cbeg = v.cbeg; a.cend = v.cend;
     a.mu = x->mu.p; a.mu_per_column = mu_per_column;
-    a.npairs = k * (k + 1) / 2;
     a.lam = lam; a.c0 = std::sqrt(lam_y * M_PI / 2.0); a.hl = lam_y / 2.0;
-    // shapes of the dense kernel: pair blocks of 32 over groups of four waves with NB blocks each; column splits
-    const int nblk = (a.npairs + 31) / 32;
-    const int gy = (nblk + 23) / 24;                                 // at most 6 blocks per wave: 96 + 96 accumulator registers
-    const int need = (nblk + 4 * gy - 1) / (4 * gy);
-    const int nb = need <= 2 ? 2 : need <= 4 ? 4 : 6;
-    const int64_t tiles_all = (v.rows + yue::kExpoTile - 1) / yue::kExpoTile;
-    a.splits = splits_for(tiles_all * gy, a.nf, &a.cols_per_split);
+    const GramPlan g = gram_plan(k, v.rows, a.nf);
+    const int gy = g.gy, nb = g.nb;
+    const int64_t tiles_all = g.tiles_all;
+    a.npairs = g.npairs; a.splits = g.splits; a.cols_per_split = g.cols_per_split;
     // rows per batch: the workspace [splits][rows][npairs] fp32 within the budget, a multiple of the tile
     int64_t rows_batch = (x->gram_mb << 20) / ((int64_t)a.splits * a.npairs * 4);
     rows_batch = std::max<int64_t>(yue::kExpoTile, rows_batch / yue::kExpoTile * yue::kExpoTile);
@@ -193,9 +214,7 @@ int yue_expo_half_sweep(yue_ctx *c, int side, double lam, double lam_y, int mu_p
         const dim3 grid((unsigned)((std::max<int64_t>(dense, 0) + yue::kExpoTile - 1) / yue::kExpoTile), (unsigned)gy, (unsigned)a.splits);
         HIPCHK(hipEventRecord(x->gram_ev[(size_t)b].first, c->stream));
         if (grid.x > 0) {
-            if ((rc = nb == 2 ? launch_gram<2>(a, grid, lds_gram, c->stream) : nb == 4 ? launch_gram<4>(a, grid, lds_gram, c->stream)
-                                                                                       : launch_gram<6>(a, grid, lds_gram, c->stream)))
-                return rc;
+            if ((rc = launch_gram_nb(nb, a, grid, lds_gram, c->stream))) return rc;
         }
         HIPCHK(hipEventRecord(x->gram_ev[(size_t)b].second, c->stream));
         hipLaunchKernelGGL(yue::k_expo_solve, dim3((unsigned)(a.pos1 - a.pos0)), dim3(yue::kWrmfThreads), lds_solve, c->stream, a);
@@ -218,6 +237,48 @@ int yue_expo_half_sweep(yue_ctx *c, int side, double lam, double lam_y, int mu_p
     if (status != INT_MAX)
         return fail(YUE_ERR_ARG, std::string("yue_expo_half_sweep: non-positive pivot in the Cholesky factorisation of ") + (side == 0 ? "user" : "item") +
                                      " row " + std::to_string(status) + " (B = F^T diag(A) F + lam*I is not positive definite: raise lam)");
+    return YUE_OK;
+}
+
+int yue_expo_gram_rows(yue_ctx *c, int side, int mu_per_column, double lam_y, const int32_t *rows, int64_t nrows, double *out) {
+    yue_expo *x = nullptr;
+    int rc = common_checks(c, "yue_expo_gram_rows", &x, lam_y);
+    if (rc) return rc;
+    if ((rc = side_checks(c, "yue_expo_gram_rows", side, mu_per_column))) return rc;
+    yue_host::WrmfPairsView v;
+    if (!yue_host::wrmf_pairs_view(c, side, &v)) return fail(YUE_ERR_ARG, "yue_expo_gram_rows: call yue_expo_set_pairs first (after yue_set_factors)");
+    if (!rows || !out || nrows < 1) return fail(YUE_ERR_ARG, "yue_expo_gram_rows: rows and out must hold nrows >= 1 entries");
+    for (int64_t t = 0; t < nrows; ++t)
+        if (rows[t] < 0 || rows[t] >= v.rows) return fail(YUE_ERR_ARG, "yue_expo_gram_rows: rows[" + std::to_string(t) + "] is outside the side's rows");
+    HIPCHK(hipSetDevice(c->device));
+    const int k = c->k;
+    yue::ExpoArgs a{};
+    a.F = side == 0 ? c->Q.p : c->P.p; a.nf = side == 0 ? c->n : c->m;
+    a.X = side == 0 ? c->P.p : c->Q.p; a.nr = v.rows; a.k = k;
+    a.mu = x->mu.p; a.mu_per_column = mu_per_column;
+    a.c0 = std::sqrt(lam_y * M_PI / 2.0); a.hl = lam_y / 2.0;
+    // the production shapes: those of a half-sweep over ALL the side's rows, not of this list
+    const GramPlan g = gram_plan(k, v.rows, a.nf);
+    a.npairs = g.npairs; a.splits = g.splits; a.cols_per_split = g.cols_per_split;
+    const size_t cells = (size_t)a.splits * (size_t)nrows * (size_t)a.npairs;
+    if (cells * 4 > ((size_t)x->gram_mb << 20)) return fail(YUE_ERR_ARG, "yue_expo_gram_rows: the list's Grams do not fit expo_gram_mb");
+    HIPCHK(x->gws.resize(cells));
+    HIPCHK(x->rows.resize((size_t)nrows));
+    HIPCHK(hipMemcpyAsync(x->rows.p, rows, (size_t)nrows * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    a.sched = x->rows.p; a.gws = x->gws.p;
+    a.pos0 = 0; a.pos1 = nrows;
+    const dim3 grid((unsigned)((nrows + yue::kExpoTile - 1) / yue::kExpoTile), (unsigned)g.gy, (unsigned)a.splits);
+    if ((rc = launch_gram_nb(g.nb, a, grid, yue::expo_dyn_lds(k), c->stream))) return rc;
+    HIPCHK(hipGetLastError());
+    std::vector<float> host(cells);
+    HIPCHK(hipMemcpyAsync(host.data(), x->gws.p, cells * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const size_t per = (size_t)nrows * (size_t)a.npairs;
+    for (size_t e = 0; e < per; ++e) {                               // the splits in order in fp64, as k_expo_solve sums them
+        double s = 0.0;
+        for (int sp = 0; sp < a.splits; ++sp) s += (double)host[(size_t)sp * per + e];
+        out[e] = s;
+    }
     return YUE_OK;
 }
 
