@@ -121,7 +121,7 @@ int yue_epoch_plan(int64_t m, int k, int64_t round_events, double events_total, 
 
 /* The default round size of yue_bpr_epoch for the uploaded factors on this device.  One resident set of waves of the
  * round kernel takes 57,344 events on MI355X at k = 128 (49,152 for the kernels that finish contended rows inside
- * the launch: option round_fold / round_meta = 0, and yue_bpr_rounds); the default is up to 6 such sets, as long as
+ * the launch: option round_meta = 0, and yue_bpr_rounds); the default is up to 6 such sets, as long as
  * a round holds at most four events per item row of this rank (job-wide average on a communicator: the call is then
  * collective), at most 4 sets for rounds with fewer than two touches per item row -- 344,064 on BASELINE config 3,
  * 172,032 on config 2.  Results depend on the round size (DESIGN.md section 3 tabulates the distance from the

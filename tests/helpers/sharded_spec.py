@@ -8,7 +8,7 @@ import numpy as np
 from yue_amd import synth
 from yue_amd.dist import user_block_width
 
-SEED_RANK = 0x632BE59BD9B4E019       # per-shard sampler stream, as in csrc/yue_hip.hip
+SEED_RANK = 0x632BE59BD9B4E019       # per-shard sampler stream, as in csrc/bpr_host.hip
 
 
 def shard_problem(rank, m, n_local, d, k):

@@ -102,7 +102,7 @@ def test_one_rank_spec_equals_plain_rounds(orc):
 
 def test_epoch_schedule_of_the_library_for_eight_ranks_on_config4():
     # BASELINE config 4: 10M users, 500M events over 8 item shards, k = 128; the library's host arithmetic
-    # (yue_hip.hip: yue_epoch_plan, used by yue_bpr_epoch on every rank) against the Python restatement
+    # (bpr_host.hip: yue_epoch_plan, used by yue_bpr_epoch on every rank) against the Python restatement
     from yue_amd._shim import epoch_plan
     from yue_amd.dist import epoch_block_plan, user_block_width
     m, k, etot = 10000000, 128, 500e6

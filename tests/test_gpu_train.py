@@ -655,3 +655,73 @@ def test_epoch_with_users_of_more_than_one_header_segment(orc, k):
     P, Q = dev.get_factors()
     dev.close()
     assert rel_err(P, Po) < TOL and rel_err(Q, Qo) < TOL
+
+
+_INSTANCE_REF = {}
+
+
+def _instance_problem(orc, k):
+    """One contended problem per factor width, with the round-semantics oracle's result (computed once, never written to):
+    600 users x 20 events on 400 items in rounds of about 1024 events -- 12 rounds, five touches per item row and round,
+    and at least 16 workgroups per launch at every events-per-wave setting."""
+    if k not in _INSTANCE_REF:
+        m, n, d, W = 600, 400, 20, 1024
+        data, P0, Q0, ev_u = _synth_problem(m, n, d, k, seed=41)
+        rp = np.array(epoch_round_ptr(data['ev_ptr'], W), np.int64)
+        assert len(rp) - 1 >= 10
+        j = orc.sample_counter(17, 0, ev_u, n, data['indptr'], data['indices'])
+        Po, Qo = P0.copy(), Q0.copy()
+        nll_o = orc.bpr_rounds(Po, Qo, ev_u, data['ev_i'], j, rp, 0.02, 0.01, 0.01)
+        _INSTANCE_REF[k] = (data, P0, Q0, ev_u, rp, j, W, nll_o, Po, Qo)
+    return _INSTANCE_REF[k]
+
+
+# every events-per-wave setting yue_set_option accepts once factors of width k are uploaded (k = 64, 128, 130: one, two and
+# four registers per lane and row); the last pair passes the option and has no kernel instance
+@pytest.mark.parametrize('k,tpw', [(64, 0), (64, 2), (64, 4), (64, 8), (64, 16), (128, 0), (128, 2), (128, 4), (128, 8),
+                                   (130, 0), (130, 4), (130, 2)])
+def test_every_round_kernel_instance_matches_the_oracle(orc, k, tpw):
+    """Each (k, events per wave) pair through the three callers of the round kernels: (a) the epoch path with user rows under
+    round semantics (k_round_m<KR,TPW> + k_round_fold), (b) the epoch path with round_meta = 0 (k_round<KR,TPW>), (c) the same
+    triplets through yue_bpr_rounds (k_round<KR,TPW>).  All three have the semantics of orc_bpr_rounds."""
+    from yue_amd._shim import Device, YueHipError
+    data, P0, Q0, ev_u, rp, j, W, nll_o, Po, Qo = _instance_problem(orc, k)
+    dev = Device(0, raise_errors=True)
+    dev.set_factors(P0, Q0)
+    dev.set_interactions(data['indptr'], data['indices'], data['ev_ptr'], data['ev_i'])
+    dev.set_option('round_tpw', tpw)
+    dev.set_option('round_user_seq', 0)
+
+    def epoch():
+        return dev.bpr_epoch(17, 0, W, 0.02, 0.01, 0.01)[0]
+
+    def rounds():
+        return dev.bpr_rounds(ev_u, data['ev_i'], j, rp, 0.02, 0.01, 0.01)
+
+    for way, meta, run in (('a', 1, epoch), ('b', 0, epoch), ('c', 1, rounds)):
+        dev.set_option('round_meta', meta)
+        if (k, tpw) == (130, 2):
+            with pytest.raises(YueHipError, match=r'unsupported \(k, TPW\) combination'):
+                run()
+            continue
+        dev.set_factors(P0, Q0)
+        nll = run()
+        if run is epoch:
+            assert dev.get_option('round_path') == meta and dev.get_option('round_last_user_seq') == 0
+        P, Q = dev.get_factors()
+        print('k=%d tpw=%d (%s): rel P %.2e Q %.2e, nll %.3e' % (k, tpw, way, rel_err(P, Po), rel_err(Q, Qo), abs(nll - nll_o) / abs(nll_o)))
+        assert rel_err(P, Po) < TOL and rel_err(Q, Qo) < TOL, way
+        assert abs(nll - nll_o) <= 1e-9 * abs(nll_o), way
+    if (k, tpw) == (130, 2):
+        # the refused launches left the device usable: a default epoch (the module's current user-row option) on the factors
+        # uploaded before them matches its oracle
+        dev.set_option('round_tpw', 0)
+        dev.set_option('round_meta', 1)
+        dev.set_option('round_user_seq', _SEQ[0])
+        nll, _, _ = dev.bpr_epoch(17, 0, W, 0.02, 0.01, 0.01)
+        P1, Q1 = P0.copy(), Q0.copy()
+        nll_1 = _epoch_oracle(orc)(P1, Q1, ev_u, data['ev_i'], j, rp, 0.02, 0.01, 0.01)
+        P, Q = dev.get_factors()
+        assert dev.get_option('round_last_user_seq') == _SEQ[0]
+        assert rel_err(P, P1) < TOL and rel_err(Q, Q1) < TOL and abs(nll - nll_1) <= 1e-9 * abs(nll_1)
+    dev.close()

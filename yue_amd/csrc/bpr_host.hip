@@ -1,5 +1,5 @@
 // libyue_hip.so -- BPR training entry points: exact replay by dependency levels, S-rounds, fused epochs, CUNE's steps, the
-// TF-style Adam step, options and kernel timing (include/yue_hip.h).
+// TF-style Adam step and kernel timing (include/yue_hip.h).
 #include "host_common.hpp"
 
 #include "train_kernels.hpp"
@@ -7,7 +7,9 @@
 
 using yue_host::fail;
 using yue_host::kr_of;
-static_assert(yue::kNllSlots == yue_host::kNllSlotsHost && yue::kHeaderSlack == yue_host::kHeaderSlackHost, "host_common.hpp mirrors these");
+using yue_host::with_kr;
+static_assert(yue::kNllSlots == yue_host::kNllSlotsHost && yue::kHeaderSlack == yue_host::kHeaderSlackHost &&
+              yue::kMetaStageMax == (uint32_t)yue_host::kMetaStageMaxHost, "host_common.hpp mirrors these");
 
 namespace {
 
@@ -31,21 +33,30 @@ void launch_level(yue_ctx *c, const yue::TrainArgs &a, int64_t e0, int64_t e1) {
     const int tpw = (int)std::min<int64_t>(64, std::max<int64_t>(1, (e1 - e0) / 4096));
     const int64_t waves = (e1 - e0 + tpw - 1) / tpw;
     const dim3 grid((unsigned)((waves + 3) / 4)), block(256);
-    switch (kr_of(c->k)) {
-        case 1: hipLaunchKernelGGL(yue::k_bpr_level<1>, grid, block, 0, c->stream, a, e0, e1, tpw); break;
-        case 2: hipLaunchKernelGGL(yue::k_bpr_level<2>, grid, block, 0, c->stream, a, e0, e1, tpw); break;
-        default: hipLaunchKernelGGL(yue::k_bpr_level<4>, grid, block, 0, c->stream, a, e0, e1, tpw); break;
-    }
+    with_kr(c->k, [&](auto kr) { hipLaunchKernelGGL(yue::k_bpr_level<kr()>, grid, block, 0, c->stream, a, e0, e1, tpw); });
 }
 
-// `meta`: for k_round_m (update launch on pre-pass metadata) instead of k_round
-int tpw_of(const yue_ctx *c, bool meta) {
-    if (c->opt_round_tpw) return c->opt_round_tpw;
-    // measured: k = 128 (C3): 8 events per wave 53.9 ms/epoch, 4 -> 58.7, 16 -> 60.7; k = 64 (C2): k_round 16 events per wave
-    // 5.2 ms/epoch, 8 -> 5.7; k_round_m + fold (round 3, profiles/r03_round_w_stage_sweep.txt) 8 -> 3.0 ms, 16 -> 3.3
-    const int kr = kr_of(c->k);
-    return kr == 4 ? 4 : kr == 2 ? 8 : meta ? 8 : 16;
+// The (KR, TPW) instances of k_round / k_round_m: registers per lane and row, events per wave.  This list is the only place
+// that names them: the occupancy query, both launches and the defaults below go through with_round_instance.
+constexpr int kRoundInstances[][2] = {{1, 8}, {1, 16}, {2, 8}, {4, 4}, {1, 4}, {2, 4}, {1, 2}, {2, 2}};
+
+// Default events per wave; `meta`: for k_round_m (update launch on pre-pass metadata) instead of k_round.
+// measured: k = 128 (C3): 8 events per wave 53.9 ms/epoch, 4 -> 58.7, 16 -> 60.7; k = 64 (C2): k_round 16 events per wave
+// 5.2 ms/epoch, 8 -> 5.7; k_round_m + fold (round 3, profiles/r03_round_w_stage_sweep.txt) 8 -> 3.0 ms, 16 -> 3.3
+constexpr int default_round_tpw(int kr, bool meta) { return kr == 4 ? 4 : kr == 2 ? 8 : meta ? 8 : 16; }
+
+// f(integral_constant KR, integral_constant TPW) for the instance (kr, tpw); false when the list has no such instance
+template <class F, size_t... I>
+bool with_round_instance(int kr, int tpw, F &&f, std::index_sequence<I...>) {
+    return ((kr == kRoundInstances[I][0] && tpw == kRoundInstances[I][1] &&
+             (f(std::integral_constant<int, kRoundInstances[I][0]>{}, std::integral_constant<int, kRoundInstances[I][1]>{}), true)) || ...);
 }
+template <class F>
+bool with_round_instance(int kr, int tpw, F &&f) {
+    return with_round_instance(kr, tpw, f, std::make_index_sequence<sizeof kRoundInstances / sizeof kRoundInstances[0]>{});
+}
+
+int tpw_of(const yue_ctx *c, bool meta) { return c->opt_round_tpw ? c->opt_round_tpw : default_round_tpw(kr_of(c->k), meta); }
 
 // Epoch path: the pre-pass over all rounds (k_round_meta) -- one LDS word per item row of a range, ranges of at most
 // kMetaRangeMax rows.  Past kMetaRangesMax ranges every work item would re-read its round too often: the caller then
@@ -59,7 +70,6 @@ constexpr double kRoundEventsPerItemRow = 4.0;
 // their ranges first (k_round_bucket), so that a work item reads its own touches only.
 bool meta_bucketed(const yue_ctx *c) { return c->n > kMetaRangeMax * kMetaRangesMax || c->opt_round_bucket; }
 bool meta_path_fits(const yue_ctx *c) { return c->opt_round_meta && c->n <= ((int64_t)yue::kBucketRangesMax << yue::kBucketShift); }
-bool fold_path(const yue_ctx *c) { return meta_path_fits(c); }
 
 // Default round size.
 //   * k_round / k_round_m with the retire phase inside the launch: the events ONE resident set of waves takes (workgroups
@@ -73,26 +83,15 @@ bool fold_path(const yue_ctx *c) { return meta_path_fits(c); }
 //     rounds of 6 sets with staging blocks sized for them are 6 % faster than rounds of 3.
 // `n_rows` = item rows per rank (job-wide average on a communicator, so that all ranks agree).
 int default_round_events(yue_ctx *c, double n_rows, int64_t *out) {
-    const bool fold = fold_path(c);
+    const bool fold = yue_host::fold_path(c);
     const int tpw = tpw_of(c, fold);
     int per_cu = 0, cus = 0;
     hipError_t e = hipSuccess;
-#define YUE_OCC(KR_, TPW_) \
-    e = fold ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, yue::k_round_m<KR_, TPW_>, 256, 0) \
-             : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, yue::k_round<KR_, TPW_>, 256, 0); \
-    break;
-    switch (kr_of(c->k) * 16 + tpw) {
-        case 1 * 16 + 8: YUE_OCC(1, 8)
-        case 1 * 16 + 16: YUE_OCC(1, 16)
-        case 2 * 16 + 8: YUE_OCC(2, 8)
-        case 4 * 16 + 4: YUE_OCC(4, 4)
-        case 1 * 16 + 4: YUE_OCC(1, 4)
-        case 2 * 16 + 4: YUE_OCC(2, 4)
-        case 1 * 16 + 2: YUE_OCC(1, 2)
-        case 2 * 16 + 2: YUE_OCC(2, 2)
-        default: return fail(YUE_ERR_ARG, "unsupported (k, TPW) combination");
-    }
-#undef YUE_OCC
+    if (!with_round_instance(kr_of(c->k), tpw, [&](auto kr, auto t) {
+            e = fold ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, yue::k_round_m<kr(), t()>, 256, 0)
+                     : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, yue::k_round<kr(), t()>, 256, 0);
+        }))
+        return fail(YUE_ERR_ARG, "unsupported (k, TPW) combination");
     HIPCHK(e);
     // A CU admits at most floor(800 / (ceil(SGPRs / 16) * 16 + 16)) workgroups of 4 waves whatever the occupancy query
     // says (MI355X_MICROARCH.md, residency rule; seen on C2: the query answers 7, a round sized for 7 runs as two
@@ -117,7 +116,7 @@ int default_round_events(yue_ctx *c, double n_rows, int64_t *out) {
 }
 
 // One S-round launch: update [e0,e1) with the counts in cnt_cur, prepare [n0,n1) into cnt_next.
-// Every timing_stride-th launch is bracketed with HIP events on the library's stream.
+// (Kernel timing brackets all round launches of a call once, in run_rounds, not the single launch.)
 int launch_round(yue_ctx *c, const yue::TrainArgs &a_in, int64_t e0, int64_t e1, int64_t n0, int64_t n1,
                  int parity, int apply_p) {
     unsigned long long *cnt[2] = {c->cnt0.p, c->cnt1.p};
@@ -145,17 +144,10 @@ int launch_round(yue_ctx *c, const yue::TrainArgs &a_in, int64_t e0, int64_t e1,
 #else
     const yue::TrainArgs &a = a_in;
 #endif
-    switch (kr_of(c->k) * 16 + tpw) {
-        case 1 * 16 + 8: hipLaunchKernelGGL((yue::k_round<1, 8>), grid, block, 0, c->stream, a, ra, a.ev_u, a.ev_i, a.ev_j); break;
-        case 1 * 16 + 16: hipLaunchKernelGGL((yue::k_round<1, 16>), grid, block, 0, c->stream, a, ra, a.ev_u, a.ev_i, a.ev_j); break;
-        case 2 * 16 + 8: hipLaunchKernelGGL((yue::k_round<2, 8>), grid, block, 0, c->stream, a, ra, a.ev_u, a.ev_i, a.ev_j); break;
-        case 4 * 16 + 4: hipLaunchKernelGGL((yue::k_round<4, 4>), grid, block, 0, c->stream, a, ra, a.ev_u, a.ev_i, a.ev_j); break;
-        case 1 * 16 + 4: hipLaunchKernelGGL((yue::k_round<1, 4>), grid, block, 0, c->stream, a, ra, a.ev_u, a.ev_i, a.ev_j); break;
-        case 2 * 16 + 4: hipLaunchKernelGGL((yue::k_round<2, 4>), grid, block, 0, c->stream, a, ra, a.ev_u, a.ev_i, a.ev_j); break;
-        case 1 * 16 + 2: hipLaunchKernelGGL((yue::k_round<1, 2>), grid, block, 0, c->stream, a, ra, a.ev_u, a.ev_i, a.ev_j); break;
-        case 2 * 16 + 2: hipLaunchKernelGGL((yue::k_round<2, 2>), grid, block, 0, c->stream, a, ra, a.ev_u, a.ev_i, a.ev_j); break;
-        default: return fail(YUE_ERR_ARG, "unsupported (k, TPW) combination");
-    }
+    if (!with_round_instance(kr_of(c->k), tpw, [&](auto kr, auto t) {
+            hipLaunchKernelGGL((yue::k_round<kr(), t()>), grid, block, 0, c->stream, a, ra, a.ev_u, a.ev_i, a.ev_j);
+        }))
+        return fail(YUE_ERR_ARG, "unsupported (k, TPW) combination");
     return YUE_OK;
 }
 
@@ -222,11 +214,7 @@ void launch_round_fold(yue_ctx *c, const yue::TrainArgs &a, int64_t e0, int64_t 
     yue::FoldArgs f{};
     f.fold = c->fold.p + yue::fold_base(e0, round_index); f.round_rows = c->round_rows.p + round_index; f.Q = a.Q; f.dQ = a.dQ; f.stage = a.stage; f.k = c->k; f.capacity = (uint32_t)((e1 - e0) & ~(int64_t)3);
     const dim3 fgrid((unsigned)std::min<int64_t>(c->opt_fold_blocks, std::max<int64_t>(1, (e1 - e0 + 15) / 16))), block(256);
-    switch (kr_of(c->k)) {
-        case 1: hipLaunchKernelGGL(yue::k_round_fold<1>, fgrid, block, 0, c->stream, f); break;
-        case 2: hipLaunchKernelGGL(yue::k_round_fold<2>, fgrid, block, 0, c->stream, f); break;
-        default: hipLaunchKernelGGL(yue::k_round_fold<4>, fgrid, block, 0, c->stream, f); break;
-    }
+    with_kr(c->k, [&](auto kr) { hipLaunchKernelGGL(yue::k_round_fold<kr()>, fgrid, block, 0, c->stream, f); });
 }
 
 int launch_round_m(yue_ctx *c, const yue::TrainArgs &a_in, int64_t e0, int64_t e1, int64_t round_index) {
@@ -250,27 +238,19 @@ int launch_round_m(yue_ctx *c, const yue::TrainArgs &a_in, int64_t e0, int64_t e
     const yue::TrainArgs &a = a_in;
 #endif
     const uint32_t *mi = c->meta_i.p, *mj = c->meta_j.p;
-    if (c->bigq) {              // (the default events-per-wave instances only)
-        switch (kr_of(c->k) * 16 + tpw) {
-            case 1 * 16 + 8: hipLaunchKernelGGL((yue::k_round_m<1, 8, true>), grid, block, 0, c->stream, a, ra, a.ev_u, a.ev_i, a.ev_j, mi, mj); break;
-            case 2 * 16 + 8: hipLaunchKernelGGL((yue::k_round_m<2, 8, true>), grid, block, 0, c->stream, a, ra, a.ev_u, a.ev_i, a.ev_j, mi, mj); break;
-            case 4 * 16 + 4: hipLaunchKernelGGL((yue::k_round_m<4, 4, true>), grid, block, 0, c->stream, a, ra, a.ev_u, a.ev_i, a.ev_j, mi, mj); break;
-            default: return fail(YUE_ERR_ARG, "item matrices of 2 GiB and more: only the default events-per-wave setting (round_tpw = 0)");
-        }
-    } else
-#define YUE_RM(KR_, TPW_) hipLaunchKernelGGL((yue::k_round_m<KR_, TPW_>), grid, block, 0, c->stream, a, ra, a.ev_u, a.ev_i, a.ev_j, mi, mj); break;
-    switch (kr_of(c->k) * 16 + tpw) {
-        case 1 * 16 + 8: YUE_RM(1, 8)
-        case 1 * 16 + 16: YUE_RM(1, 16)
-        case 2 * 16 + 8: YUE_RM(2, 8)
-        case 4 * 16 + 4: YUE_RM(4, 4)
-        case 1 * 16 + 4: YUE_RM(1, 4)
-        case 2 * 16 + 4: YUE_RM(2, 4)
-        case 1 * 16 + 2: YUE_RM(1, 2)
-        case 2 * 16 + 2: YUE_RM(2, 2)
-        default: return fail(YUE_ERR_ARG, "unsupported (k, TPW) combination");
-    }
-#undef YUE_RM
+    if (c->bigq) {              // (64-bit row pointers: the default events-per-wave instances only)
+        bool is_default = false;
+        with_round_instance(kr_of(c->k), tpw, [&](auto kr, auto t) {
+            if constexpr (t() == default_round_tpw(kr(), true)) {
+                hipLaunchKernelGGL((yue::k_round_m<kr(), t(), true>), grid, block, 0, c->stream, a, ra, a.ev_u, a.ev_i, a.ev_j, mi, mj);
+                is_default = true;
+            }
+        });
+        if (!is_default) return fail(YUE_ERR_ARG, "item matrices of 2 GiB and more: only the default events-per-wave setting (round_tpw = 0)");
+    } else if (!with_round_instance(kr_of(c->k), tpw, [&](auto kr, auto t) {
+                   hipLaunchKernelGGL((yue::k_round_m<kr(), t()>), grid, block, 0, c->stream, a, ra, a.ev_u, a.ev_i, a.ev_j, mi, mj);
+               }))
+        return fail(YUE_ERR_ARG, "unsupported (k, TPW) combination");
     launch_round_fold(c, a, e0, e1, round_index);
     return YUE_OK;
 }
@@ -284,14 +264,10 @@ int launch_round_u(yue_ctx *c, const yue::TrainArgs &a, int64_t u0, int64_t u1, 
     if (blocks == 0) return YUE_OK;
     const dim3 grid((unsigned)blocks), block(256);
     const uint32_t *mi = c->meta_i.p, *mj = c->meta_j.p;
-#define YUE_RU(KR_) do { if (c->opt_round_fast) hipLaunchKernelGGL((yue::k_round_u<KR_, true>), grid, block, 0, c->stream, a, ra, a.ev_i, a.ev_j, mi, mj); \
-                         else hipLaunchKernelGGL((yue::k_round_u<KR_, false>), grid, block, 0, c->stream, a, ra, a.ev_i, a.ev_j, mi, mj); } while (0)
-    switch (kr_of(c->k)) {
-        case 1: YUE_RU(1); break;
-        case 2: YUE_RU(2); break;
-        default: YUE_RU(4); break;
-    }
-#undef YUE_RU
+    with_kr(c->k, [&](auto kr) {
+        if (c->opt_round_fast) hipLaunchKernelGGL((yue::k_round_u<kr(), true>), grid, block, 0, c->stream, a, ra, a.ev_i, a.ev_j, mi, mj);
+        else hipLaunchKernelGGL((yue::k_round_u<kr(), false>), grid, block, 0, c->stream, a, ra, a.ev_i, a.ev_j, mi, mj);
+    });
     launch_round_fold(c, a, e0, e1, round_index);
     return YUE_OK;
 }
@@ -387,10 +363,11 @@ void reset_round_state(yue_ctx *c) {
     (void)hipStreamSynchronize(c->stream);
 }
 
-
 }  // namespace
 
 namespace yue_host {
+bool fold_path(const yue_ctx *c) { return meta_path_fits(c); }
+
 int zero_scalars(yue_ctx *c) {
     HIPCHK(hipMemsetAsync(c->scal.p, 0, (yue::kNllSlots + 8) * sizeof(double), c->stream));
     return YUE_OK;
@@ -463,7 +440,7 @@ int yue_bpr_replay(yue_ctx *c, const int32_t *u, const int32_t *i, const int32_t
     }
     std::vector<int64_t> lptr((size_t)nlev + 2, 0);
     for (int64_t t = 0; t < T; ++t) if (lvl[(size_t)t] > 0) lptr[(size_t)lvl[(size_t)t] + 1]++;
-    for (int32_t l = 1; l <= nlev + 0; ++l) lptr[(size_t)l + 1] += lptr[(size_t)l];
+    for (int32_t l = 1; l <= nlev; ++l) lptr[(size_t)l + 1] += lptr[(size_t)l];
     const int64_t Tv = lptr[(size_t)nlev + 1];
     std::vector<int32_t> pu((size_t)std::max<int64_t>(Tv, 1)), pi((size_t)std::max<int64_t>(Tv, 1)), pj((size_t)std::max<int64_t>(Tv, 1));
     {
@@ -537,11 +514,7 @@ int yue_cune_steps(yue_ctx *c, const int32_t *u, const int32_t *i, const int32_t
     a.inv_s = 1.0 / s; a.inv_s32 = (float)(1.0 / s); a.lr = lr;
     a.ru = (float)(lr * regU); a.ri = (float)(lr * regI);          // CUNE.py:156: python-float product, cast to float32 by NumPy
     a.loss_out = c->x_loss.p;
-    switch (kr_of(c->k)) {
-        case 1: hipLaunchKernelGGL(yue::k_cune_steps<1>, dim3(1), dim3(64), 0, c->stream, a); break;
-        case 2: hipLaunchKernelGGL(yue::k_cune_steps<2>, dim3(1), dim3(64), 0, c->stream, a); break;
-        default: hipLaunchKernelGGL(yue::k_cune_steps<4>, dim3(1), dim3(64), 0, c->stream, a); break;
-    }
+    with_kr(c->k, [&](auto kr) { hipLaunchKernelGGL(yue::k_cune_steps<kr()>, dim3(1), dim3(64), 0, c->stream, a); });
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(loss_out, c->x_loss.p, T * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -574,11 +547,7 @@ int yue_adam_step(yue_ctx *c, const int32_t *u, const int32_t *i, const int32_t 
     a.U = c->P.p; a.V = c->Q.p; a.gU = c->dP.p; a.gV = c->dQ.p; a.k = c->k; a.u = c->xu.p; a.i = c->xi.p; a.j = c->xj.p; a.T = T;
     a.reg = (float)reg; a.loss_slots = c->scal.p;
     const dim3 grid((unsigned)(((T + 31) / 32 + 3) / 4));
-    switch (kr_of(c->k)) {
-        case 1: hipLaunchKernelGGL(yue::k_mb_grad<1>, grid, dim3(256), 0, c->stream, a); break;
-        case 2: hipLaunchKernelGGL(yue::k_mb_grad<2>, grid, dim3(256), 0, c->stream, a); break;
-        default: hipLaunchKernelGGL(yue::k_mb_grad<4>, grid, dim3(256), 0, c->stream, a); break;
-    }
+    with_kr(c->k, [&](auto kr) { hipLaunchKernelGGL(yue::k_mb_grad<kr()>, grid, dim3(256), 0, c->stream, a); });
     // tf.train.AdamOptimizer defaults; lr_t as _prepare / _apply_sparse_shared form it
     const double b1 = 0.9, b2 = 0.999;
     const float lr_t = (float)(lr * std::sqrt(1.0 - std::pow(b2, (double)step)) / (1.0 - std::pow(b1, (double)step)));
@@ -780,144 +749,6 @@ int yue_get_kernel_timing(yue_ctx *c, double *total_ms, int64_t *launches, int64
     if (triplets) *triplets = trip;
     c->ev_used = 0;
     return YUE_OK;
-}
-
-int yue_get_scan_stats(yue_ctx *c, double *kernel_ms, int64_t *events, int64_t *rescored, int *used_bf16) {
-    if (!c) return fail(YUE_ERR_ARG, "null context");
-    if (kernel_ms) *kernel_ms = c->scan_ms;
-    if (events) *events = c->scan_events;
-    if (rescored) *rescored = c->scan_rescored;
-    if (used_bf16) *used_bf16 = c->scan_used_bf16;
-    return YUE_OK;
-}
-
-int yue_get_scan_work(yue_ctx *c, int64_t *tiles_scored, int64_t *tiles_total) {
-    if (!c) return fail(YUE_ERR_ARG, "null context");
-    if (tiles_scored) *tiles_scored = c->scan_tiles_done;
-    if (tiles_total) *tiles_total = c->scan_tiles_total;
-    return YUE_OK;
-}
-
-int yue_get_option(yue_ctx *c, const char *name, int64_t *value) {
-    if (!c || !name || !value) return fail(YUE_ERR_ARG, "yue_get_option: null argument");
-    const std::string key(name);
-    if (key == "scan_f32") *value = c->opt_scan_f32;
-    else if (key == "scan_batch") *value = c->opt_scan_batch;
-    else if (key == "scan_two_phase") *value = c->opt_scan_two_phase;
-    else if (key == "fism_lds") *value = c->opt_fism_lds;
-    else if (key == "fism_inplace") *value = c->opt_fism_inplace;
-    else if (key == "scan_growth") *value = c->opt_scan_growth;
-    else if (key == "scan_filter_ub") *value = c->opt_scan_filter_ub;
-    else if (key == "scan_streams") *value = c->opt_scan_streams;
-    else if (key == "scan_slabs") *value = c->opt_scan_slabs;
-    else if (key == "scan_streams_min_users") *value = c->opt_scan_streams_min_users;
-    else if (key == "scan_last_chunks") *value = c->scan_chunks;
-    else if (key == "scan_last_few_users") *value = c->scan_few_users;
-    else if (key == "scan_last_settle") *value = c->scan_settle;
-    else if (key == "topn_true") *value = c->opt_topn_true;
-    else if (key == "round_stage") *value = c->opt_round_stage;
-    else if (key == "round_last_stage_max") *value = c->last_stage_max;
-    else if (key == "round_meta") *value = c->opt_round_meta;
-    else if (key == "comm_group_mb") *value = c->opt_comm_group_mb;
-    else if (key == "round_cus_reserved") *value = c->opt_round_cus_reserved;
-    else if (key == "comm_last_compute_waits") *value = c->comm_compute_waits;
-    else if (key == "round_user_seq") *value = c->opt_round_user_seq;
-    else if (key == "round_fast") *value = c->opt_round_fast;
-    else if (key == "round_last_user_seq") *value = c->last_round_user_seq;
-    else if (key == "round_bucket") *value = c->opt_round_bucket;
-    else if (key == "fold_blocks") *value = c->opt_fold_blocks;
-    else if (key == "round_tpw") *value = c->opt_round_tpw;
-    else if (key == "epoch_exact") *value = c->opt_epoch_exact;
-    else if (key == "replay_levels") *value = c->opt_replay_levels;
-    else if (key == "chain_waves") *value = c->opt_chain_waves;
-    else if (key == "chain_split") *value = c->opt_chain_split;
-    else if (key == "chain_fast") *value = c->opt_chain_fast;
-    else if (key == "chain_xcd") *value = c->opt_chain_xcd;
-    else if (key == "chain_last_us") *value = c->chain_kernel_us;
-    else if (key == "chain_ring") *value = c->opt_chain_ring;
-    else if (key == "chain_spin") *value = c->opt_chain_spin;
-    else if (key == "chain_last_runs") *value = c->chain_runs;          // last exact launch: runs walked, waves launched
-    else if (key == "chain_last_waves") *value = c->chain_waves;
-    else if (key == "replay_last_levels") *value = c->replay_levels;    // last levelled replay: dependency levels = launches
-    // which kernels yue_bpr_epoch runs for the uploaded factors: 0 k_round, 1 k_round_meta + k_round_m + k_round_fold
-    else if (key == "round_path") *value = fold_path(c) ? 1 : 0;
-    else if (key.compare(0, 5, "wrmf_") == 0) return yue_host::wrmf_get_option(c, key, value);
-    else if (key.compare(0, 4, "knn_") == 0) return yue_host::knn_get_option(c, key, value);
-    else if (key.compare(0, 4, "ipf_") == 0) return yue_host::ipf_get_option(c, key, value);
-    else if (key.compare(0, 5, "expo_") == 0) return yue_host::expo_get_option(c, key, value);
-    else if (key.compare(0, 4, "cof_") == 0) return yue_host::cof_get_option(c, key, value);
-    else return fail(YUE_ERR_ARG, "yue_get_option: unknown option " + key);
-    return YUE_OK;
-}
-
-int yue_set_option(yue_ctx *c, const char *name, int64_t value) {
-    if (!c || !name) return fail(YUE_ERR_ARG, "yue_set_option: null argument");
-    const std::string key(name);
-    if (key == "scan_f32") { c->opt_scan_f32 = value != 0; return YUE_OK; }
-    if (key == "scan_batch") { if (value != 0 && value != 1) return fail(YUE_ERR_ARG, "yue_set_option: scan_batch must be 0 or 1"); c->opt_scan_batch = (int)value; return YUE_OK; }
-    if (key == "topn_true") { c->opt_topn_true = value != 0; return YUE_OK; }
-    if (key == "scan_two_phase") { c->opt_scan_two_phase = value != 0; return YUE_OK; }
-    if (key == "fism_lds") { c->opt_fism_lds = value != 0; return YUE_OK; }
-    if (key == "fism_inplace") { c->opt_fism_inplace = value != 0; return YUE_OK; }
-    if (key == "scan_streams_min_users") { if (value < 1024) return fail(YUE_ERR_ARG, "yue_set_option: scan_streams_min_users must be at least 1024"); c->opt_scan_streams_min_users = value; return YUE_OK; }
-    if (key == "scan_slabs") { if (value < 2 || value > 64) return fail(YUE_ERR_ARG, "yue_set_option: scan_slabs must be 2..64"); c->opt_scan_slabs = (int)value; return YUE_OK; }
-    if (key == "scan_streams") { if (value != 1 && value != 2) return fail(YUE_ERR_ARG, "yue_set_option: scan_streams must be 1 or 2"); c->opt_scan_streams = (int)value; return YUE_OK; }
-    if (key == "scan_filter_ub") { if (value < 1 || value > 3) return fail(YUE_ERR_ARG, "yue_set_option: scan_filter_ub must be 1, 2 or 3"); c->opt_scan_filter_ub = (int)value; return YUE_OK; }
-    if (key == "scan_growth") { if (value != 0 && (value < 2 || value > 64)) return fail(YUE_ERR_ARG, "yue_set_option: scan_growth must be 0 (automatic) or 2..64"); c->opt_scan_growth = (int)value; return YUE_OK; }
-    if (key == "round_stage") {
-        if (value < 0 || value > (int64_t)yue::kMetaStageMax) return fail(YUE_ERR_ARG, "yue_set_option: round_stage must be 0, 1 or 2..64");
-        c->opt_round_stage = (int)value; return YUE_OK;
-    }
-    if (key == "round_meta") { c->opt_round_meta = value != 0; return YUE_OK; }
-    if (key == "comm_group_mb") { if (value < 1 || value > 4096) return fail(YUE_ERR_ARG, "yue_set_option: comm_group_mb must be 1..4096"); c->opt_comm_group_mb = (int)value; return YUE_OK; }
-    if (key == "round_cus_reserved") {
-        // the compute stream is re-created with a CU mask that leaves the LAST `value` CUs of the device free: RCCL's kernels
-        // (collective stream, no mask) find room beside round launches that would otherwise fill the chip exactly
-        int cus = 0;
-        HIPCHK(hipSetDevice(c->device));
-        HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
-        if (value < 0 || value >= cus) return fail(YUE_ERR_ARG, "yue_set_option: round_cus_reserved must be 0 .. CUs - 1");
-        HIPCHK(hipStreamSynchronize(c->stream));
-        hipStream_t fresh = nullptr;
-        if (value == 0) HIPCHK(hipStreamCreateWithFlags(&fresh, hipStreamNonBlocking));
-        else {
-            std::vector<uint32_t> mask((size_t)(cus + 31) / 32, 0u);
-            for (int cu = 0; cu < cus - (int)value; ++cu) mask[(size_t)cu / 32] |= 1u << (cu % 32);
-            HIPCHK(hipExtStreamCreateWithCUMask(&fresh, (uint32_t)mask.size(), mask.data()));
-        }
-        (void)hipStreamDestroy(c->stream);
-        c->stream = fresh;
-        c->opt_round_cus_reserved = (int)value;
-        return YUE_OK;
-    }
-    if (key == "round_user_seq") { c->opt_round_user_seq = value != 0; return YUE_OK; }
-    if (key == "round_fast") { c->opt_round_fast = value != 0; return YUE_OK; }
-    if (key == "epoch_exact") { c->opt_epoch_exact = value != 0; return YUE_OK; }
-    if (key == "replay_levels") { c->opt_replay_levels = value != 0; return YUE_OK; }
-    if (key == "chain_split") { if (value < -1 || value > 1) return fail(YUE_ERR_ARG, "yue_set_option: chain_split must be -1, 0 or 1"); c->opt_chain_split = (int)value; return YUE_OK; }
-    if (key == "chain_fast") { c->opt_chain_fast = value != 0; return YUE_OK; }
-    if (key == "chain_xcd") { c->opt_chain_xcd = value != 0; return YUE_OK; }
-    if (key == "chain_ring") { if (value != 0 && value != 8 && value != 16) return fail(YUE_ERR_ARG, "yue_set_option: chain_ring must be 0, 8 or 16"); c->opt_chain_ring = (int)value; return YUE_OK; }
-    if (key == "chain_waves") { if (value < 0 || value > 8) return fail(YUE_ERR_ARG, "yue_set_option: chain_waves must be 0..8"); c->opt_chain_waves = (int)value; return YUE_OK; }
-    if (key == "chain_spin") { if (value < 0 || value > 0x7fffffff) return fail(YUE_ERR_ARG, "yue_set_option: chain_spin out of range"); c->opt_chain_spin = value; return YUE_OK; }
-    if (key == "round_bucket") { c->opt_round_bucket = value != 0; return YUE_OK; }
-    if (key == "fold_blocks") { if (value < 1 || value > 65536) return fail(YUE_ERR_ARG, "yue_set_option: fold_blocks out of range"); c->opt_fold_blocks = (int)value; return YUE_OK; }
-#ifdef YUE_STAMPS
-    if (key == "debug_stamp_launch") { c->stamp_launch = value; c->update_launches = 0; return YUE_OK; }
-#endif
-    if (key == "round_tpw") {
-        if (value != 0 && value != 2 && value != 4 && value != 8 && value != 16) return fail(YUE_ERR_ARG, "yue_set_option: round_tpw must be 0, 2, 4, 8 or 16");
-        if (value == 8 && kr_of(c->k) == 4) return fail(YUE_ERR_ARG, "yue_set_option: round_tpw 8 needs k <= 128");
-        if (value == 16 && kr_of(c->k) != 1) return fail(YUE_ERR_ARG, "yue_set_option: round_tpw 16 needs k <= 64");
-        c->opt_round_tpw = (int)value;
-        return YUE_OK;
-    }
-    if (key.compare(0, 5, "wrmf_") == 0) return yue_host::wrmf_set_option(c, key, value);
-    if (key.compare(0, 4, "knn_") == 0) return yue_host::knn_set_option(c, key, value);
-    if (key.compare(0, 4, "ipf_") == 0) return yue_host::ipf_set_option(c, key, value);
-    if (key.compare(0, 5, "expo_") == 0) return yue_host::expo_set_option(c, key, value);
-    if (key.compare(0, 4, "cof_") == 0) return yue_host::cof_set_option(c, key, value);
-    return fail(YUE_ERR_ARG, "yue_set_option: unknown option " + key);
 }
 
 #ifdef YUE_STAMPS

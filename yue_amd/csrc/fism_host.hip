@@ -4,7 +4,7 @@
 #include "fism_kernels.hpp"
 
 using yue_host::fail;
-using yue_host::kr_of;
+using yue_host::with_kr;
 
 extern "C" {
 
@@ -70,11 +70,7 @@ int yue_fism_epoch(yue_ctx *c, const int64_t *user_ptr, int64_t m, const int32_t
     a.P = c->fP.p; a.Q = c->fQ.p; a.Bi = c->fBi.p; a.n = c->fn; a.k = c->fk;
     a.user_ptr = c->f_ptr.p; a.m = m; a.ev_i = c->f_items.p; a.negs = c->f_negs.p; a.rho = rho; a.coef = c->f_coef.p;
     a.lr = lr; a.regI = regI; a.regB = regB; a.x_rows = c->f_x.p; a.out = sc;
-    switch (kr_of(c->fk)) {
-        case 1: hipLaunchKernelGGL(yue::k_fism_epoch<1>, dim3(1), dim3(64), 0, c->stream, a); break;
-        case 2: hipLaunchKernelGGL(yue::k_fism_epoch<2>, dim3(1), dim3(64), 0, c->stream, a); break;
-        default: hipLaunchKernelGGL(yue::k_fism_epoch<4>, dim3(1), dim3(64), 0, c->stream, a); break;
-    }
+    with_kr(c->fk, [&](auto kr) { hipLaunchKernelGGL(yue::k_fism_epoch<kr()>, dim3(1), dim3(64), 0, c->stream, a); });
     hipLaunchKernelGGL(yue::k_fism_sumsq, dim3(256), dim3(256), 0, c->stream, c->fP.p, c->fQ.p, c->fBi.p, c->fn, c->fk, sc + 1);
     HIPCHK(hipGetLastError());
     double h[4];
@@ -146,12 +142,9 @@ int yue_fism_rounds(yue_ctx *c, const int64_t *user_ptr, int64_t m, const int32_
             HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
             const bool start = 2 * lds_rows <= 160u * 1024u && std::min(m, round_users) <= (int64_t)cus * (int64_t)((160u * 1024u) / (2 * lds_rows));
             const size_t lds_launch = start ? 2 * lds_rows : lds;
-            const void *kfn = nullptr;
-            switch (kr_of(c->fk)) {
-                case 1: kfn = start ? (const void *)yue::k_fism_round_lds<1, true> : (const void *)yue::k_fism_round_lds<1, false>; break;
-                case 2: kfn = start ? (const void *)yue::k_fism_round_lds<2, true> : (const void *)yue::k_fism_round_lds<2, false>; break;
-                default: kfn = start ? (const void *)yue::k_fism_round_lds<4, true> : (const void *)yue::k_fism_round_lds<4, false>; break;
-            }
+            const void *kfn = with_kr(c->fk, [&](auto kr) {
+                return start ? (const void *)yue::k_fism_round_lds<kr(), true> : (const void *)yue::k_fism_round_lds<kr(), false>;
+            });
             HIPCHK(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_launch));
             const dim3 apply_grid((unsigned)std::min<int64_t>(1024, (int64_t)(nk + 255) / 256));
             for (int64_t u0 = 0; u0 < m; u0 += round_users) {
@@ -230,11 +223,7 @@ int yue_fism_rounds(yue_ctx *c, const int64_t *user_ptr, int64_t m, const int32_
         const int64_t u1 = std::min(m, u0 + round_users);
         ra.u_begin = u0; ra.u_end = u1; ra.w_base = uq_ptr[(size_t)u0];
         const dim3 grid((unsigned)((u1 - u0 + 3) / 4));
-        switch (kr_of(c->fk)) {
-            case 1: hipLaunchKernelGGL(yue::k_fism_round<1>, grid, dim3(256), 0, c->stream, a, ra); break;
-            case 2: hipLaunchKernelGGL(yue::k_fism_round<2>, grid, dim3(256), 0, c->stream, a, ra); break;
-            default: hipLaunchKernelGGL(yue::k_fism_round<4>, grid, dim3(256), 0, c->stream, a, ra); break;
-        }
+        with_kr(c->fk, [&](auto kr) { hipLaunchKernelGGL(yue::k_fism_round<kr()>, grid, dim3(256), 0, c->stream, a, ra); });
         hipLaunchKernelGGL(yue::k_fism_apply, apply_grid, dim3(256), 0, c->stream, c->fP.p, c->fQ.p, c->fBi.p, c->f_dP.p, c->f_dQ.p, c->f_dB.p, c->fn, c->fk);
     }
     hipLaunchKernelGGL(yue::k_fism_sumsq, dim3(256), dim3(256), 0, c->stream, c->fP.p, c->fQ.p, c->fBi.p, c->fn, c->fk, sc + 1);

@@ -1,8 +1,9 @@
 // Host side of libyue_hip.so, shared by its translation units: the opaque context (device buffers, streams, options),
 // error plumbing, and the few helpers more than one subsystem uses.  The C ABI is include/yue_hip.h.
-//   core_host.hip   context, factors, interactions            bpr_host.hip   replay levels, S-rounds, epochs, CUNE, Adam, options
-//   chain_host.hip  exact sequential semantics as dataflow    scan_host.hip  predict + evalRanking's selection
+//   core_host.hip   context, factors, interactions            bpr_host.hip   replay levels, S-rounds, epochs, CUNE, Adam, kernel timing
+//   chain_host.hip  exact sequential semantics as dataflow    scan_host.hip  predict + evalRanking's selection, scan statistics
 //   fism_host.hip   FISM                                      comm.hip       RCCL
+//   options_host.hip  yue_get_option / yue_set_option: the option table (no device code)
 //   wrmf_host.hip   WRMF (ALS half-sweeps)                     knn_host.hip   UserKNN (neighbours, ranking)
 //   ipf_host.hip    IPF (session-graph ranking)                expo_host.hip  ExpoMF (exposure-weighted ALS, MFMA Gram)
 //   cof_host.hip    CoFactor (co-occurrence, level-scheduled item sweep)
@@ -17,6 +18,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 struct ncclComm;
@@ -54,8 +56,19 @@ struct DevBuf {
 
 constexpr int kNllSlotsHost = 1024;   // == yue::kNllSlots (bpr_device.hpp; checked where both are visible)
 constexpr int kHeaderSlackHost = 16;  // == yue::kHeaderSlack (round_kernels.hpp)
+constexpr int kMetaStageMaxHost = 64; // == yue::kMetaStageMax (round_kernels.hpp)
 
 inline int kr_of(int k) { return k <= 64 ? 1 : k <= 128 ? 2 : 4; }   // registers per lane per row (64 lanes)
+
+// f(std::integral_constant<int, KR>{}) with KR = kr_of(k): picks the <1> / <2> / <4> instance of a kernel template
+template <class F>
+auto with_kr(int k, F &&f) {
+    switch (kr_of(k)) {
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        default: return f(std::integral_constant<int, 4>{});
+    }
+}
 
 }  // namespace yue_host
 
@@ -200,6 +213,8 @@ struct yue_ctx {
 
 namespace yue_host {
 inline bool on_communicator(const yue_ctx *c) { return c->comm != nullptr || c->seam_reduce != nullptr; }
+// bpr_host.hip: yue_bpr_epoch runs k_round_meta + k_round_m / k_round_u + k_round_fold for the uploaded factors (else k_round)
+bool fold_path(const yue_ctx *c);
 // bpr_host.hip: loss / scalar scratch shared by the training entry points
 int zero_scalars(yue_ctx *c);
 int read_scalars(yue_ctx *c, double *nll, double *sp, double *sq);

@@ -1,4 +1,4 @@
-// libyue_hip.so -- predict and evalRanking's selection (include/yue_hip.h).
+// libyue_hip.so -- predict, evalRanking's selection and the statistics of the last scan (include/yue_hip.h).
 #include "host_common.hpp"
 
 #include "score2_kernels.hpp"
@@ -221,6 +221,22 @@ int yue_topn_scan(yue_ctx *c, const int32_t *users, int64_t nu, int N, const int
     c->scan_tiles_done = (int64_t)work[0];
     c->scan_tiles_total = ((nu + 31) / 32) * ntile;
     if (flags[0]) return fail(YUE_ERR_FEW_ITEMS, "a user has fewer than N candidate items (the reference raises IndexError, base/IterativeRecommender.py:126)");
+    return YUE_OK;
+}
+
+int yue_get_scan_stats(yue_ctx *c, double *kernel_ms, int64_t *events, int64_t *rescored, int *used_bf16) {
+    if (!c) return fail(YUE_ERR_ARG, "null context");
+    if (kernel_ms) *kernel_ms = c->scan_ms;
+    if (events) *events = c->scan_events;
+    if (rescored) *rescored = c->scan_rescored;
+    if (used_bf16) *used_bf16 = c->scan_used_bf16;
+    return YUE_OK;
+}
+
+int yue_get_scan_work(yue_ctx *c, int64_t *tiles_scored, int64_t *tiles_total) {
+    if (!c) return fail(YUE_ERR_ARG, "null context");
+    if (tiles_scored) *tiles_scored = c->scan_tiles_done;
+    if (tiles_total) *tiles_total = c->scan_tiles_total;
     return YUE_OK;
 }
 

@@ -199,7 +199,7 @@ class ControlPlane(object):
 
 def user_block_width(round_events, events_total, m, world):
     """Users per round on a communicator: the same number on every rank, derived from job-wide
-    counts only (mirror of the rule in csrc/yue_hip.hip: yue_bpr_epoch)."""
+    counts only (mirror of the rule in csrc/bpr_host.hip: yue_bpr_epoch)."""
     per_user = float(events_total) / world / m
     return max(1, int(math.floor(round_events / max(per_user, 1e-9) + 0.5)))
 
@@ -214,7 +214,7 @@ def epoch_round_ptr(ev_ptr, round_events, events_total=None, world=1):
 
 
 def epoch_block_plan(m, k, round_events, events_total, world):
-    """The host-side schedule of yue_bpr_epoch (csrc/yue_hip.hip): user-block width, blocks per apply / all-reduce
+    """The host-side schedule of yue_bpr_epoch (csrc/bpr_host.hip): user-block width, blocks per apply / all-reduce
     group (at least ~8 MB of user-factor differences per collective), and the groups as (first user, one past the
     last user, float32 elements all-reduced).  The same on every rank by construction."""
     ub = user_block_width(round_events, events_total, m, world)
