@@ -406,6 +406,47 @@ int yue_ipf_set_graph(yue_ctx *ctx, int64_t m, int64_t n, const int64_t *u_ptr, 
 int yue_ipf_predict(yue_ctx *ctx, int32_t user, int64_t cap, int32_t *items_out, double *scores_out, int64_t *len_out);
 int yue_ipf_topn(yue_ctx *ctx, const int32_t *users, int64_t nu, int N, int32_t *ids_out, double *scores_out, int32_t *len_out);
 
+/*
+ * CUNE's user-network stage (reference recommender/advanced/CUNE.py:34-118) -- collaborative user network, random walks,
+ * CBOW user embedding, cosine top-K friends.  Needs no factors.  Contract: tests/helpers/numpy_cune_net.py, DESIGN.md 18.
+ * Every random number is cnet_hash(seed ^ tag, a, b, c, d) (csrc/cnet_kernels.hpp: the mix64 chain of the BPR sampler).
+ *   yue_cnet_set_pairs     the distinct (user, item) pairs both ways, as yue_knn_set_pairs takes them (no counts).  The
+ *                        network CUNet[a] = every other user b repeated |items(a) & items(b)| times is never built: entry
+ *                        r of it is found from the prefix sums of deg(item) - 1 over a's item row.  A user whose total is 0
+ *                        is not in the network: no walks, no embedding row, no friends.
+ *   yue_cnet_walks         T walks of length L (2 <= L <= 64, T (L - 1) <= 15360) from every network user, one wave per
+ *                        start user; draw (start, t, step, attempt) picks entry mulhi(hash, total) of CUNet[last].  Up to
+ *                        10 re-draws while the candidate is in visited[start] (:64-69) -- consulted only where the walk
+ *                        stands on its start user; for any other node the set counts as empty (the reference reads there
+ *                        what walks from that node have stored so far, which depends on dict order: stated deviation).
+ *                        The walks (user ascending, t ascending) are stored in the order of (hash(seed ^ shuffle, walk),
+ *                        walk) -- shuffle(self.walks), :74 -- and stay on the device.  walks_out [nw][L] may be NULL.
+ *   yue_cnet_set_walks     uploads walks of the caller's (ids below m) in training order instead.
+ *   yue_cnet_embed         Word2Vec(walks, size=dim, window, min_count=0, iter=epochs) as gensim documents it, with this
+ *                        stream: CBOW with the mean of the context, `negative` negatives from the unigram^0.75 table of the
+ *                        walks' user counts (a draw equal to the word is skipped), window shrink b uniform in [0, window)
+ *                        per position, subsampling at 1e-3, alpha from 0.025 to 1e-4 linear in the words passed (one value
+ *                        per walk), no update where |logit| >= 6, syn0 = (U - 0.5) / dim, syn1neg = 0; float32.  A round
+ *                        is round_walks consecutive walks (0: the default, 64): each walk reads the rows as the round began
+ *                        plus its own changes; its row differences are rounded to multiples of 2^-36 and summed as 64-bit
+ *                        integers (order-free), then row = fp32(fp64(row) + sum 2^-36).  Bit-reproducible; round_walks = 1
+ *                        is the sequential algorithm.  1 <= dim <= 128; L (negative + 2) rows of dim floats must fit
+ *                        60 KiB.  W_out [m][dim] (may be NULL): rows of users outside the walks are 0.
+ *   yue_cnet_set_embedding uploads an embedding of the caller's; `users` (ascending, or NULL: all m) have rows.
+ *   yue_cnet_friends       for every user with a row the K (1 <= K <= 100) others with the largest cosine(W[a], W[b]) =
+ *                        dot / sqrt(n_a n_b), dots and norms in fp64 over the float32 values (tool/qmath.py:36-45; 0 where
+ *                        a norm is 0, the reference's ZeroDivisionError branch), by (cosine descending, id ascending).
+ *                        friends_out [m][K] padded with -1, sims_out [m][K] padded with 0; either may be NULL.
+ * Read-only option "cnet_last_ns": device time of the last walks / embed / friends call.
+ */
+int yue_cnet_set_pairs(yue_ctx *ctx, int64_t m, int64_t n, const int64_t *u_ptr, const int32_t *u_items, const int64_t *i_ptr,
+                       const int32_t *i_users, int64_t nnz);
+int yue_cnet_walks(yue_ctx *ctx, int T, int L, uint64_t seed, int32_t *walks_out, int64_t *nw_out);
+int yue_cnet_set_walks(yue_ctx *ctx, int64_t m, int64_t nw, int L, const int32_t *walks);
+int yue_cnet_embed(yue_ctx *ctx, int dim, int window, int epochs, int negative, int64_t round_walks, uint64_t seed, float *W_out);
+int yue_cnet_set_embedding(yue_ctx *ctx, int64_t m, int dim, const float *W, const int32_t *users, int64_t nu);
+int yue_cnet_friends(yue_ctx *ctx, int K, int32_t *friends_out, double *sims_out);
+
 /* Multi-GPU (one process per GPU, RCCL over xGMI).  Rank 0 creates the id, the caller ships
  * the 128 bytes to the other ranks (any side channel), every rank calls yue_comm_init. */
 int yue_comm_unique_id(void *id128_out);

@@ -1,0 +1,71 @@
+"""CPU: the NumPy contract of CUNE's user-network stage (tests/helpers/numpy_cune_net.py) against the reference's own
+outputs (tests/golden/g15_cune_*, tools/make_cune_net_goldens.py): the implicit network's (prefix, item, listener) rule
+against CUNet of CUNE.py:39-52, friends and cosines against topKSim of :88-95, friends' items against :104-114."""
+from collections import Counter
+
+import numpy as np
+import pytest
+
+from helpers import numpy_cune_net as cn
+from util import gz
+
+
+def test_implicit_network_is_the_reference_cunet():
+    z = gz('g15_cune_net_c1.npz')
+    m, n = int(z['m']), int(z['n'])
+    (up, ui), (ip, iu) = cn.pairs_from_events(z['ev_u'], z['ev_i'], m, n)
+    net = cn.Net(up, ui, ip, iu)
+    ptr, nb, mult = z['ptr'], z['nb'].astype(np.int64), z['mult'].astype(np.int64)
+    in_net = 0
+    for a in range(m):
+        lo, hi = ptr[a], ptr[a + 1]
+        assert net.total[a] == mult[lo:hi].sum(), a                   # the reference's list length; 0 for users outside it
+        got = Counter(net.entry(a, r) for r in range(int(net.total[a])))
+        assert got == dict(zip(nb[lo:hi].tolist(), mult[lo:hi].tolist())), a
+        in_net += hi > lo
+    assert in_net == len(net.users) > 0
+
+
+@pytest.fixture(scope='module')
+def friends_case():
+    z = gz('g15_cune_friends.npz')
+    ids, sims = cn.friends(z['W'], z['net'], int(z['K']))
+    return z, ids, sims
+
+
+def test_friends_and_cosines_are_the_reference_topksim(friends_case):
+    z, ids, sims = friends_case
+    assert np.array_equal(ids, z['ids'])
+    assert np.abs(sims - z['sims']).max() <= 1e-12
+    assert (ids[z['net']] >= 0).all() and len(z['net']) == int(z['m'])
+    gaps = -np.diff(z['sims'], axis=1)                                # the seeded W leaves no near-tie to excuse
+    assert gaps.min() > 1e-9
+
+
+def test_friends_items_are_the_reference_ipositiveset(friends_case):
+    z, ids, _ = friends_case
+    m, n = int(z['m']), int(z['n'])
+    (up, ui), _ = cn.pairs_from_events(z['ev_u'], z['ev_i'], m, n)
+    got = cn.friend_items(z['net'], ids, up, ui)
+    for u in range(m):
+        assert got.get(u, []) == z['ip_items'][z['ip_ptr'][u]:z['ip_ptr'][u + 1]].tolist(), u
+    assert z['ip_ptr'][-1] > 0
+
+
+def test_zero_row_takes_the_reference_zero_division_branch():
+    W = np.abs(np.random.RandomState(3).randn(6, 5)).astype(np.float32)
+    W[2] = 0
+    assert cn.cosine(W[2], W[1]) == 0 and cn.cosine(W[2], W[2]) == 0
+    ids, sims = cn.friends(W, np.arange(6), 5)
+    assert (ids[[0, 1, 3, 4, 5], -1] == 2).all()                      # positive rows: the zero row ranks last
+    assert ids[2].tolist() == [0, 1, 3, 4, 5] and (sims[2] == 0).all()
+
+
+def test_walk_contract_takes_the_redraw_cutoff_on_a_clique():
+    ev_u = np.repeat(np.arange(6), 2)
+    ev_i = np.tile([0, 1], 6)
+    (up, ui), (ip, iu) = cn.pairs_from_events(ev_u, ev_i, 6, 2)
+    stats = {}
+    w = cn.walks(cn.Net(up, ui, ip, iu), 20, 10, 1, stats)
+    assert w.shape == (120, 10) and stats['cutoffs'] >= 1
+    assert (w[:, 1:] != w[:, :-1]).all()                              # a user is never its own neighbour

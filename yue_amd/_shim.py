@@ -29,7 +29,8 @@ SYMBOLS = ['yue_last_error', 'yue_version', 'yue_ctx_create', 'yue_ctx_destroy',
            'yue_expo_set_pairs', 'yue_expo_set_mu', 'yue_expo_get_mu', 'yue_expo_half_sweep', 'yue_expo_update_mu', 'yue_expo_gram_rows',
            'yue_cof_cooccur', 'yue_cof_get_cooccur', 'yue_cof_set_sppmi', 'yue_cof_set_state', 'yue_cof_get_state', 'yue_cof_item_sweep',
            'yue_knn_set_pairs', 'yue_knn_neighbors', 'yue_knn_predict', 'yue_knn_topn',
-           'yue_ipf_set_graph', 'yue_ipf_predict', 'yue_ipf_topn']
+           'yue_ipf_set_graph', 'yue_ipf_predict', 'yue_ipf_topn',
+           'yue_cnet_set_pairs', 'yue_cnet_walks', 'yue_cnet_set_walks', 'yue_cnet_embed', 'yue_cnet_set_embedding', 'yue_cnet_friends']
 
 
 class YueHipError(RuntimeError):
@@ -105,6 +106,7 @@ class Device(object):
         self.m = self.n = self.k = self.E = 0
         self.knn_m = self.knn_n = 0
         self.ipf_m = self.ipf_n = 0
+        self.cnet_m = self.cnet_dim = 0
         self._chk(self._lib.yue_ctx_create(C.c_int(device), C.byref(self._ctx)))
 
     # reference convention: print, exit(-1)
@@ -529,6 +531,57 @@ class Device(object):
         self._chk(self._lib.yue_ipf_topn(self._ctx, up, C.c_int64(nu), C.c_int(N), ids.ctypes.data_as(C.POINTER(C.c_int32)),
                                          scores.ctypes.data_as(C.POINTER(C.c_double)), lens.ctypes.data_as(C.POINTER(C.c_int32))))
         return ids, scores, lens
+
+    # -- CUNE's user-network stage (needs no factors) --------------------------------------------
+    def cnet_set_pairs(self, m, n, u_ptr, u_items, i_ptr, i_users):
+        """Distinct pairs both ways: user-major (items ascending) and item-major (users ascending)."""
+        u_ptr, a = _i64(u_ptr)
+        i_ptr, e = _i64(i_ptr)
+        assert len(u_ptr) == m + 1 and len(i_ptr) == n + 1, 'cnet_set_pairs: pointer sizes must be m + 1, n + 1'
+        nnz = int(u_ptr[-1])
+        assert int(i_ptr[-1]) == nnz and len(u_items) == nnz and len(i_users) == nnz, 'cnet_set_pairs: both directions must hold nnz pairs'
+        u_items, b = _i32(u_items if nnz else np.zeros(1, np.int32))
+        i_users, f = _i32(i_users if nnz else np.zeros(1, np.int32))
+        self._chk(self._lib.yue_cnet_set_pairs(self._ctx, C.c_int64(m), C.c_int64(n), a, b, e, f, C.c_int64(nnz)))
+        self.cnet_m = int(m)
+
+    def cnet_walks(self, T, L, seed):
+        """int32 [nw, L]: T walks per network user in training (shuffled) order; they stay on the device for cnet_embed."""
+        out = np.empty((self.cnet_m * max(int(T), 0), max(int(L), 0)), np.int32)
+        nw = C.c_int64()
+        self._chk(self._lib.yue_cnet_walks(self._ctx, C.c_int(T), C.c_int(L), C.c_uint64(seed), out.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(nw)))
+        return out.reshape(-1)[:nw.value * int(L)].reshape(nw.value, int(L))
+
+    def cnet_set_walks(self, m, walks):
+        walks, p = _i32(walks)
+        assert walks.ndim == 2
+        self._chk(self._lib.yue_cnet_set_walks(self._ctx, C.c_int64(m), C.c_int64(walks.shape[0]), C.c_int(walks.shape[1]), p))
+        self.cnet_m = int(m)
+
+    def cnet_embed(self, dim, window, epochs, seed, negative=5, round_walks=0):
+        """float32 [m, dim]: the CBOW user embedding of the walks on the device (rows of users outside the walks are 0)."""
+        W = np.empty((self.cnet_m, max(int(dim), 0)), np.float32)
+        self._chk(self._lib.yue_cnet_embed(self._ctx, C.c_int(dim), C.c_int(window), C.c_int(epochs), C.c_int(negative), C.c_int64(round_walks),
+                                           C.c_uint64(seed), W.ctypes.data_as(C.POINTER(C.c_float))))
+        self.cnet_dim = int(dim)
+        return W
+
+    def cnet_set_embedding(self, W, users=None):
+        W, p = _f32(W)
+        assert W.ndim == 2
+        up, nu = None, 0
+        if users is not None:
+            users, up = _i32(users)
+            nu = len(users)
+        self._chk(self._lib.yue_cnet_set_embedding(self._ctx, C.c_int64(W.shape[0]), C.c_int(W.shape[1]), p, up, C.c_int64(nu)))
+        self.cnet_m, self.cnet_dim = W.shape
+
+    def cnet_friends(self, K):
+        """(friends int32 [m, K] -1 padded, cosines float64 [m, K] 0 padded) by (cosine desc, id asc)."""
+        friends = np.empty((self.cnet_m, max(int(K), 0)), np.int32)
+        sims = np.empty((self.cnet_m, max(int(K), 0)), np.float64)
+        self._chk(self._lib.yue_cnet_friends(self._ctx, C.c_int(K), friends.ctypes.data_as(C.POINTER(C.c_int32)), sims.ctypes.data_as(C.POINTER(C.c_double))))
+        return friends, sims
 
     def comm_init(self, unique_id, rank, nranks):
         buf = (C.c_ubyte * UNIQUE_ID_BYTES).from_buffer_copy(unique_id)

@@ -1,0 +1,326 @@
+// libyue_hip.so -- CUNE's user-network stage (recommender/advanced/CUNE.py:34-118): implicit collaborative user network,
+// random walks, CBOW user embedding in rounds, cosine top-K friends (include/yue_hip.h).  Kernels: cnet_kernels.hpp.
+// Needs no factors: the state is the pair lists of yue_cnet_set_pairs, the walks and the embedding.
+#include "host_common.hpp"
+
+#include "cnet_kernels.hpp"
+
+#include <numeric>
+
+using yue_host::fail;
+
+struct yue_cnet {
+    int64_t m = 0, n = 0, nnz = 0;               // pairs (m == 0: none)
+    DevBuf<int64_t> u_ptr, i_ptr, pref, total, dest;
+    DevBuf<int32_t> u_items, i_users;
+    std::vector<int32_t> net_pairs;              // users with total > 0, ascending
+    // walks, in training (shuffled) order
+    int64_t wm = 0, nw = 0;                      // wm: users the walk ids are below
+    int L = 0;
+    DevBuf<int32_t> walks, cnt, list, list_n, net, friends;
+    // embedding
+    int64_t em = 0, nnet = 0;                    // em == 0: none
+    int dim = 0;
+    DevBuf<float> syn0, syn1;
+    DevBuf<long long> acc0, acc1;
+    DevBuf<int> flag0, flag1;
+    DevBuf<uint64_t> keep, cum;
+    DevBuf<double> norm, sims;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    int64_t last_ns = 0;
+};
+
+namespace yue_host {
+
+void cnet_release(yue_ctx *c) {
+    yue_cnet *k = c->cnet;
+    if (!k) return;
+    k->u_ptr.release(); k->i_ptr.release(); k->pref.release(); k->total.release(); k->dest.release(); k->u_items.release(); k->i_users.release();
+    k->walks.release(); k->cnt.release(); k->list.release(); k->list_n.release(); k->net.release(); k->friends.release();
+    k->syn0.release(); k->syn1.release(); k->acc0.release(); k->acc1.release(); k->flag0.release(); k->flag1.release();
+    k->keep.release(); k->cum.release(); k->norm.release(); k->sims.release();
+    for (auto &e : k->ev) if (e) (void)hipEventDestroy(e);
+    delete k;
+    c->cnet = nullptr;
+}
+
+int cnet_set_option(yue_ctx *, const std::string &key, int64_t) { return fail(YUE_ERR_ARG, "yue_set_option: unknown option " + key); }
+
+int cnet_get_option(yue_ctx *c, const std::string &key, int64_t *value) {
+    if (key == "cnet_last_ns") *value = c->cnet ? c->cnet->last_ns : 0;        // device time of the last walks / embed / friends call
+    else return fail(YUE_ERR_ARG, "yue_get_option: unknown option " + key);
+    return YUE_OK;
+}
+
+}  // namespace yue_host
+
+namespace {
+
+constexpr int kDefaultRoundWalks = 64;       // chosen by the planted-groups quality test
+
+int cnet_state(yue_ctx *c, yue_cnet **out) {
+    if (!c->cnet) {
+        HIPCHK(hipSetDevice(c->device));
+        yue_cnet *k = new yue_cnet();
+        c->cnet = k;
+        for (auto &e : k->ev) HIPCHK(hipEventCreate(&e));
+    }
+    *out = c->cnet;
+    return YUE_OK;
+}
+
+// ptr[rows + 1] from 0 to nnz, ids sorted-unique in [0, bound)
+int check_csr(const int64_t *ptr, const int32_t *ids, int64_t rows, int64_t bound, int64_t nnz, const char *what) {
+    const std::string at = std::string("yue_cnet_set_pairs: ") + what;
+    if (!ptr || (nnz > 0 && !ids)) return fail(YUE_ERR_ARG, at + ": null array");
+    if (ptr[0] != 0 || ptr[rows] != nnz) return fail(YUE_ERR_ARG, at + " pointer must run from 0 to nnz");
+    for (int64_t r = 0; r < rows; ++r) {
+        if (ptr[r + 1] < ptr[r]) return fail(YUE_ERR_ARG, at + " pointer must be non-decreasing");
+        for (int64_t e = ptr[r]; e < ptr[r + 1]; ++e)
+            if (ids[e] < 0 || ids[e] >= bound || (e > ptr[r] && ids[e] <= ids[e - 1]))
+                return fail(YUE_ERR_ARG, at + " rows must hold sorted, unique ids in range");
+    }
+    return YUE_OK;
+}
+
+template <typename T>
+int upload(DevBuf<T> &buf, const T *src, int64_t count) {
+    HIPCHK(buf.resize((size_t)std::max<int64_t>(count, 1)));
+    if (count > 0) HIPCHK(hipMemcpy(buf.p, src, (size_t)count * sizeof(T), hipMemcpyHostToDevice));
+    return YUE_OK;
+}
+
+int stop_clock(yue_ctx *c, yue_cnet *k) {
+    HIPCHK(hipEventRecord(k->ev[1], c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    float ms = 0.0f;
+    HIPCHK(hipEventElapsedTime(&ms, k->ev[0], k->ev[1]));
+    k->last_ns = (int64_t)(1e6 * (double)ms);
+    return YUE_OK;
+}
+
+// the walks on the device changed: whatever was trained on the old ones is gone
+void new_walks(yue_cnet *k, int64_t wm, int64_t nw, int L) { k->wm = wm; k->nw = nw; k->L = L; k->em = 0; }
+
+}  // namespace
+
+extern "C" {
+
+int yue_cnet_set_pairs(yue_ctx *c, int64_t m, int64_t n, const int64_t *u_ptr, const int32_t *u_items, const int64_t *i_ptr,
+                       const int32_t *i_users, int64_t nnz) {
+    if (!c) return fail(YUE_ERR_ARG, "yue_cnet_set_pairs: null context");
+    if (m < 1 || n < 1 || nnz < 0 || m >= INT32_MAX || n >= INT32_MAX) return fail(YUE_ERR_ARG, "yue_cnet_set_pairs: need 1 <= m, n < 2^31 - 1 and nnz >= 0");
+    int rc = check_csr(u_ptr, u_items, m, n, nnz, "user-major");
+    if (!rc) rc = check_csr(i_ptr, i_users, n, m, nnz, "item-major");
+    if (rc) return rc;
+    {   // the item-major lists must be the transpose of the user-major ones (the skip-self index relies on it)
+        std::vector<int64_t> at(i_ptr, i_ptr + n);
+        for (int64_t u = 0; u < m; ++u)
+            for (int64_t e = u_ptr[u]; e < u_ptr[u + 1]; ++e) {
+                const int32_t i = u_items[e];
+                const int64_t q = at[(size_t)i]++;
+                if (q >= i_ptr[i + 1] || i_users[q] != (int32_t)u)
+                    return fail(YUE_ERR_ARG, "yue_cnet_set_pairs: the item-major pairs are not the transpose of the user-major pairs (item " + std::to_string(i) + ")");
+            }
+    }
+    HIPCHK(hipSetDevice(c->device));
+    yue_cnet *k = nullptr;
+    if ((rc = cnet_state(c, &k))) return rc;
+    k->m = 0;
+    if ((rc = upload(k->u_ptr, u_ptr, m + 1)) || (rc = upload(k->u_items, u_items, nnz)) || (rc = upload(k->i_ptr, i_ptr, n + 1)) ||
+        (rc = upload(k->i_users, i_users, nnz)))
+        return rc;
+    HIPCHK(k->pref.resize((size_t)std::max<int64_t>(nnz, 1)));
+    HIPCHK(k->total.resize((size_t)m));
+    yue::CnetArgs a{};
+    a.m = m; a.n = n; a.u_ptr = k->u_ptr.p; a.u_items = k->u_items.p; a.i_ptr = k->i_ptr.p; a.i_users = k->i_users.p;
+    a.pref = k->pref.p; a.total = k->total.p;
+    hipLaunchKernelGGL(yue::k_cnet_prefix, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, c->stream, a);
+    HIPCHK(hipGetLastError());
+    std::vector<int64_t> total((size_t)m);
+    HIPCHK(hipMemcpyAsync(total.data(), k->total.p, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    k->net_pairs.clear();
+    for (int64_t u = 0; u < m; ++u) if (total[(size_t)u] > 0) k->net_pairs.push_back((int32_t)u);
+    k->m = m; k->n = n; k->nnz = nnz;
+    return YUE_OK;
+}
+
+int yue_cnet_walks(yue_ctx *c, int T, int L, uint64_t seed, int32_t *walks_out, int64_t *nw_out) {
+    if (!c || !nw_out) return fail(YUE_ERR_ARG, "yue_cnet_walks: null argument");
+    yue_cnet *k = c->cnet;
+    if (!k || k->m == 0) return fail(YUE_ERR_ARG, "yue_cnet_walks: call yue_cnet_set_pairs first");
+    if (T < 1 || L < 2 || L > yue::kCnetMaxL || (int64_t)T * (L - 1) > yue::kCnetMaxVisited)
+        return fail(YUE_ERR_ARG, "yue_cnet_walks: need T >= 1, 2 <= L <= 64 and T (L - 1) <= 15360 (visited[start] lives in LDS)");
+    const int64_t nnet = (int64_t)k->net_pairs.size(), nw = nnet * T;
+    if (nw * L >= INT32_MAX) return fail(YUE_ERR_ARG, "yue_cnet_walks: more than 2^31 walk entries");
+    *nw_out = nw;
+    new_walks(k, k->m, 0, L);
+    if (nw == 0) return YUE_OK;
+    HIPCHK(hipSetDevice(c->device));
+    // shuffle(self.walks) (:74): the walks ordered by (cnet_hash(seed ^ shuffle tag, walk), walk)
+    std::vector<uint64_t> key((size_t)nw);
+    for (int64_t w = 0; w < nw; ++w) key[(size_t)w] = yue::cnet_hash(seed ^ yue::kCnetTagShuffle, (uint64_t)w, 0, 0, 0);
+    std::vector<int64_t> order((size_t)nw), dest((size_t)nw);
+    std::iota(order.begin(), order.end(), (int64_t)0);
+    std::sort(order.begin(), order.end(), [&](int64_t x, int64_t y) { return key[(size_t)x] < key[(size_t)y] || (key[(size_t)x] == key[(size_t)y] && x < y); });
+    for (int64_t r = 0; r < nw; ++r) dest[(size_t)order[(size_t)r]] = r;
+    int rc;
+    if ((rc = upload(k->dest, dest.data(), nw)) || (rc = upload(k->net, k->net_pairs.data(), nnet))) return rc;
+    HIPCHK(k->walks.resize((size_t)(nw * L)));
+    yue::CnetArgs a{};
+    a.m = k->m; a.n = k->n; a.u_ptr = k->u_ptr.p; a.u_items = k->u_items.p; a.i_ptr = k->i_ptr.p; a.i_users = k->i_users.p;
+    a.pref = k->pref.p; a.total = k->total.p; a.net = k->net.p; a.dest = k->dest.p; a.walks = k->walks.p; a.T = T; a.L = L; a.seed = seed;
+    HIPCHK(hipEventRecord(k->ev[0], c->stream));
+    hipLaunchKernelGGL(yue::k_cnet_walk, dim3((unsigned)nnet), dim3(64), (size_t)T * (L - 1) * sizeof(int32_t), c->stream, a);
+    HIPCHK(hipGetLastError());
+    if ((rc = stop_clock(c, k))) return rc;
+    if (walks_out) HIPCHK(hipMemcpy(walks_out, k->walks.p, (size_t)(nw * L) * sizeof(int32_t), hipMemcpyDeviceToHost));
+    new_walks(k, k->m, nw, L);
+    return YUE_OK;
+}
+
+int yue_cnet_set_walks(yue_ctx *c, int64_t m, int64_t nw, int L, const int32_t *walks) {
+    if (!c) return fail(YUE_ERR_ARG, "yue_cnet_set_walks: null context");
+    if (m < 1 || m >= INT32_MAX || nw < 1 || L < 2 || L > yue::kCnetMaxL || nw * L >= INT32_MAX || !walks)
+        return fail(YUE_ERR_ARG, "yue_cnet_set_walks: need 1 <= m < 2^31 - 1, nw >= 1, 2 <= L <= 64, fewer than 2^31 entries");
+    for (int64_t e = 0; e < nw * L; ++e)
+        if (walks[e] < 0 || walks[e] >= m) return fail(YUE_ERR_ARG, "yue_cnet_set_walks: user id out of range");
+    HIPCHK(hipSetDevice(c->device));
+    yue_cnet *k = nullptr;
+    int rc = cnet_state(c, &k);
+    if (rc) return rc;
+    new_walks(k, m, 0, L);
+    if ((rc = upload(k->walks, walks, nw * L))) return rc;
+    new_walks(k, m, nw, L);
+    return YUE_OK;
+}
+
+int yue_cnet_embed(yue_ctx *c, int dim, int window, int epochs, int negative, int64_t round_walks, uint64_t seed, float *W_out) {
+    if (!c) return fail(YUE_ERR_ARG, "yue_cnet_embed: null context");
+    yue_cnet *k = c->cnet;
+    if (!k || k->nw == 0) return fail(YUE_ERR_ARG, "yue_cnet_embed: call yue_cnet_walks or yue_cnet_set_walks first");
+    if (dim < 1 || dim > yue::kCnetMaxDim || window < 1 || epochs < 1 || negative < 0 || negative > 64 || round_walks < 0)
+        return fail(YUE_ERR_ARG, "yue_cnet_embed: need 1 <= dim <= 128, window >= 1, epochs >= 1, 0 <= negative <= 64, round_walks >= 0");
+    const int64_t m = k->wm, nw = k->nw;
+    const int L = k->L, rows = L * (negative + 2);
+    const size_t lds = (size_t)rows * dim * sizeof(float) + (size_t)L * (negative + 1) * sizeof(int32_t);
+    if (lds > (size_t)yue::kCnetEmbedLds)
+        return fail(YUE_ERR_ARG, "yue_cnet_embed: L (negative + 2) rows of dim floats must fit 60 KiB of LDS (a walk's working rows)");
+    if (m * dim >= ((int64_t)1 << 40)) return fail(YUE_ERR_ARG, "yue_cnet_embed: m dim is too large");
+    if (round_walks == 0) round_walks = kDefaultRoundWalks;
+    round_walks = std::min<int64_t>(round_walks, std::min<int64_t>(nw, 1 << 20));
+    HIPCHK(hipSetDevice(c->device));
+    const size_t cells = (size_t)(m * dim);
+    k->em = 0;
+    HIPCHK(k->cnt.resize((size_t)m)); HIPCHK(k->keep.resize((size_t)m)); HIPCHK(k->cum.resize((size_t)m));
+    HIPCHK(k->syn0.resize(cells)); HIPCHK(k->syn1.resize(cells)); HIPCHK(k->acc0.resize(cells)); HIPCHK(k->acc1.resize(cells));
+    HIPCHK(k->flag0.resize((size_t)m)); HIPCHK(k->flag1.resize((size_t)m));
+    HIPCHK(k->list.resize((size_t)(round_walks * rows))); HIPCHK(k->list_n.resize((size_t)round_walks));
+    HIPCHK(hipMemsetAsync(k->cnt.p, 0, (size_t)m * sizeof(int32_t), c->stream));
+    HIPCHK(hipMemsetAsync(k->acc0.p, 0, cells * sizeof(long long), c->stream));
+    HIPCHK(hipMemsetAsync(k->acc1.p, 0, cells * sizeof(long long), c->stream));
+    HIPCHK(hipMemsetAsync(k->flag0.p, 0, (size_t)m * sizeof(int), c->stream));
+    HIPCHK(hipMemsetAsync(k->flag1.p, 0, (size_t)m * sizeof(int), c->stream));
+    const int64_t words = nw * L;
+    hipLaunchKernelGGL(yue::k_cnet_count, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, c->stream, k->walks.p, words, k->cnt.p);
+    HIPCHK(hipGetLastError());
+    std::vector<int32_t> cnt((size_t)m);
+    HIPCHK(hipMemcpyAsync(cnt.data(), k->cnt.p, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    // subsampling at 1e-3 and the unigram^0.75 table, as 32-bit thresholds.  c^0.75 = sqrt(c) sqrt(sqrt(c)): correctly
+    // rounded operations only, so that the contract's NumPy gives the same bits
+    std::vector<uint64_t> keep((size_t)m, 0), cum((size_t)m, 0);
+    std::vector<int32_t> net;
+    const double thr = 1e-3 * (double)words, two32 = 4294967296.0;
+    double z = 0.0;
+    for (int64_t u = 0; u < m; ++u)
+        if (cnt[(size_t)u] > 0) { const double x = (double)cnt[(size_t)u]; z = z + std::sqrt(x) * std::sqrt(std::sqrt(x)); net.push_back((int32_t)u); }
+    double run = 0.0;
+    for (int64_t u = 0; u < m; ++u) {
+        if (cnt[(size_t)u] > 0) {
+            const double x = (double)cnt[(size_t)u];
+            const double p = (std::sqrt(x / thr) + 1.0) * (thr / x);
+            keep[(size_t)u] = p >= 1.0 ? (uint64_t)two32 : (uint64_t)(p * two32);
+            run = run + std::sqrt(x) * std::sqrt(std::sqrt(x));
+        }
+        cum[(size_t)u] = std::min<uint64_t>((uint64_t)(run / z * two32), (uint64_t)two32);
+    }
+    for (int64_t u = m - 1; u >= 0; --u) {             // the last user of the table closes it, whatever the rounding of run / z
+        cum[(size_t)u] = (uint64_t)two32;
+        if (cnt[(size_t)u] > 0) break;
+    }
+    int rc;
+    if ((rc = upload(k->keep, keep.data(), m)) || (rc = upload(k->cum, cum.data(), m)) || (rc = upload(k->net, net.data(), (int64_t)net.size()))) return rc;
+    yue::CnetEmbedArgs a{};
+    a.m = m; a.nw = nw; a.walks = k->walks.p; a.cnt = k->cnt.p; a.keep = k->keep.p; a.cum = k->cum.p;
+    a.syn0 = k->syn0.p; a.syn1 = k->syn1.p; a.acc0 = k->acc0.p; a.acc1 = k->acc1.p; a.flag0 = k->flag0.p; a.flag1 = k->flag1.p;
+    a.list = k->list.p; a.list_n = k->list_n.p;
+    a.L = L; a.dim = dim; a.window = window; a.negative = negative; a.epochs = epochs; a.seed = seed;
+    HIPCHK(hipEventRecord(k->ev[0], c->stream));
+    hipLaunchKernelGGL(yue::k_cnet_embed_init, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, c->stream, a);
+    HIPCHK(hipGetLastError());
+    for (int ep = 0; ep < epochs; ++ep)
+        for (int64_t w0 = 0; w0 < nw; w0 += round_walks) {
+            a.epoch = ep; a.w_begin = w0; a.w_count = std::min(round_walks, nw - w0);
+            if (dim <= 64) hipLaunchKernelGGL(yue::k_cnet_embed_round<1>, dim3((unsigned)a.w_count), dim3(64), lds, c->stream, a);
+            else hipLaunchKernelGGL(yue::k_cnet_embed_round<2>, dim3((unsigned)a.w_count), dim3(64), lds, c->stream, a);
+            hipLaunchKernelGGL(yue::k_cnet_embed_apply, dim3((unsigned)a.w_count), dim3(64), 0, c->stream, a);
+        }
+    HIPCHK(hipGetLastError());
+    if ((rc = stop_clock(c, k))) return rc;
+    if (W_out) HIPCHK(hipMemcpy(W_out, k->syn0.p, cells * sizeof(float), hipMemcpyDeviceToHost));
+    k->em = m; k->dim = dim; k->nnet = (int64_t)net.size();
+    return YUE_OK;
+}
+
+int yue_cnet_set_embedding(yue_ctx *c, int64_t m, int dim, const float *W, const int32_t *users, int64_t nu) {
+    if (!c) return fail(YUE_ERR_ARG, "yue_cnet_set_embedding: null context");
+    if (m < 1 || m >= INT32_MAX || dim < 1 || dim > yue::kCnetMaxDim || !W || nu < 0 || nu > m)
+        return fail(YUE_ERR_ARG, "yue_cnet_set_embedding: need 1 <= m < 2^31 - 1, 1 <= dim <= 128, 0 <= users <= m");
+    std::vector<int32_t> net;
+    if (users) {
+        for (int64_t t = 0; t < nu; ++t) {
+            if (users[t] < 0 || users[t] >= m || (t > 0 && users[t] <= users[t - 1]))
+                return fail(YUE_ERR_ARG, "yue_cnet_set_embedding: users must be ascending ids below m");
+            net.push_back(users[t]);
+        }
+    } else {
+        net.resize((size_t)m);
+        std::iota(net.begin(), net.end(), 0);
+    }
+    HIPCHK(hipSetDevice(c->device));
+    yue_cnet *k = nullptr;
+    int rc = cnet_state(c, &k);
+    if (rc) return rc;
+    k->em = 0;
+    if ((rc = upload(k->syn0, W, m * dim)) || (rc = upload(k->net, net.data(), (int64_t)net.size()))) return rc;
+    k->em = m; k->dim = dim; k->nnet = (int64_t)net.size();
+    return YUE_OK;
+}
+
+int yue_cnet_friends(yue_ctx *c, int K, int32_t *friends_out, double *sims_out) {
+    if (!c) return fail(YUE_ERR_ARG, "yue_cnet_friends: null context");
+    yue_cnet *k = c->cnet;
+    if (!k || k->em == 0) return fail(YUE_ERR_ARG, "yue_cnet_friends: call yue_cnet_embed or yue_cnet_set_embedding first");
+    if (K < 1 || K > yue::kCnetMaxK) return fail(YUE_ERR_ARG, "yue_cnet_friends: K = " + std::to_string(K) + " is not supported (1 <= K <= 100)");
+    HIPCHK(hipSetDevice(c->device));
+    const int64_t m = k->em;
+    const size_t cells = (size_t)m * (size_t)K;
+    HIPCHK(k->norm.resize((size_t)m)); HIPCHK(k->friends.resize(cells)); HIPCHK(k->sims.resize(cells));
+    yue::CnetFriendsArgs a{};
+    a.m = m; a.nnet = k->nnet; a.net = k->net.p; a.W = k->syn0.p; a.norm = k->norm.p; a.dim = k->dim; a.K = K;
+    a.friends = k->friends.p; a.sims = k->sims.p;
+    HIPCHK(hipEventRecord(k->ev[0], c->stream));
+    hipLaunchKernelGGL(yue::k_cnet_norms, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, c->stream, a);
+    if (k->nnet > 0)
+        hipLaunchKernelGGL(yue::k_cnet_friends, dim3((unsigned)((k->nnet + yue::kCnetFrQ - 1) / yue::kCnetFrQ)), dim3(yue::kCnetFrThreads), 0, c->stream, a);
+    HIPCHK(hipGetLastError());
+    int rc = stop_clock(c, k);
+    if (rc) return rc;
+    if (friends_out) HIPCHK(hipMemcpy(friends_out, k->friends.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (sims_out) HIPCHK(hipMemcpy(sims_out, k->sims.p, cells * sizeof(double), hipMemcpyDeviceToHost));
+    return YUE_OK;
+}
+
+}  // extern "C"

@@ -77,6 +77,7 @@ int yue_ctx_destroy(yue_ctx *c) {
     yue_host::ipf_release(c);
     yue_host::expo_release(c);
     yue_host::cof_release(c);
+    yue_host::cnet_release(c);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return YUE_OK;

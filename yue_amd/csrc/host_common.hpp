@@ -7,6 +7,7 @@
 //   wrmf_host.hip   WRMF (ALS half-sweeps)                     knn_host.hip   UserKNN (neighbours, ranking)
 //   ipf_host.hip    IPF (session-graph ranking)                expo_host.hip  ExpoMF (exposure-weighted ALS, MFMA Gram)
 //   cof_host.hip    CoFactor (co-occurrence, level-scheduled item sweep)
+//   cnet_host.hip   CUNE's user-network stage (walks, embedding, friends)
 #pragma once
 #include "../../include/yue_hip.h"
 
@@ -26,6 +27,7 @@ struct yue_wrmf;                                     // wrmf_host.hip: pairs, sc
 struct yue_knn;                                      // knn_host.hip: pair lists, neighbour lists, ranking buffers of UserKNN
 struct yue_expo;                                     // expo_host.hip: mu, Gram workspace, partial sums of ExpoMF
 struct yue_cof;                                      // cof_host.hip: co-occurrence CSR, SPPMI, level schedule, G / w / c of CoFactor
+struct yue_cnet;                                     // cnet_host.hip: pairs, walks, embedding, friends of CUNE's user-network stage
 struct yue_ipf;                                      // ipf_host.hip: session temporal graph, weights, per-slot work arrays of IPF
 
 namespace yue_host {
@@ -209,6 +211,7 @@ struct yue_ctx {
     yue_ipf *ipf = nullptr;              // IPF state (yue_ipf_set_graph), owned by ipf_host.hip
     yue_expo *expo = nullptr;            // ExpoMF state (yue_expo_set_mu), owned by expo_host.hip
     yue_cof *cof = nullptr;              // CoFactor state (yue_cof_*), owned by cof_host.hip
+    yue_cnet *cnet = nullptr;            // CUNE user-network state (yue_cnet_*), owned by cnet_host.hip
 };
 
 namespace yue_host {
@@ -257,4 +260,8 @@ int expo_get_option(yue_ctx *c, const std::string &key, int64_t *value);
 void cof_release(yue_ctx *c);
 int cof_set_option(yue_ctx *c, const std::string &key, int64_t value);
 int cof_get_option(yue_ctx *c, const std::string &key, int64_t *value);
+// cnet_host.hip: frees the user-network state; options "cnet_*"
+void cnet_release(yue_ctx *c);
+int cnet_set_option(yue_ctx *c, const std::string &key, int64_t value);
+int cnet_get_option(yue_ctx *c, const std::string &key, int64_t *value);
 }  // namespace yue_host

@@ -14,7 +14,7 @@ def main():
     print('CF-based Recommenders:')
     print('1. BPR   2. FISM   3. WRMF   4. IPF   5. UserKNN')
     print('Advanced Recommenders:')
-    print('a1. CUNE (training loop; needs -friends, see recommender/advanced/CUNE.py)')
+    print('a1. CUNE (friends from -net hip or -friends, see recommender/advanced/CUNE.py)')
     print('a6. ExpoMF   a7. CoFactor')
     print('=' * 80)
     order = input('Please enter the num of the algorithm to run it:')

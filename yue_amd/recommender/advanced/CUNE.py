@@ -8,11 +8,15 @@ made on the host exactly as the reference makes them (``choice`` over the friend
 listened items through ``data.listened``), so a seeded ``random`` gives the reference's stream; the loss is added up as
 the reference adds it (the regulariser once per user, :175 -- the running loss is a float32 from then on).
 
-What is NOT here: the stage that produces the friends' item sets -- the collaborative user network, the random walks and
-the Word2Vec user embedding (CUNE.py:34-118; gensim is absent in this build, parity unpinned).  The sets come from
-``CUNE=... -friends FILE`` (one line per user: ``user:friend,friend,...``; a user's friends' items are the items its
-friends listened to and the user did not, CUNE.py:115-117) or, when an ``IPositiveSet`` attribute is set on the instance
-beforehand, from there; without either every user takes the plain branch.
+The friends' item sets (the product of CUNE.py:34-118: collaborative user network, random walks, Word2Vec user embedding,
+cosine top-K friends) come from one of:
+  * ``CUNE=... -net hip [-seed N]``: the user-network stage on the device (yue_cnet_*).  gensim is
+    absent in this build, so the embedding follows gensim's documented algorithm with the library's own counter-based
+    stream (parity with gensim's output unpinned); network, walks, friends and the sets follow the reference.
+  * ``CUNE=... -friends FILE`` (one line per user: ``user:friend,friend,...``; a user's friends' items are the items its
+    friends listened to and the user did not, CUNE.py:112-114);
+  * an ``IPositiveSet`` attribute set on the instance beforehand.
+Without any of them every user takes the plain branch.
 """
 from collections import defaultdict
 from math import isnan
@@ -40,6 +44,11 @@ class CUNE(IterativeRecommender):
         self.s = float(options['-s'])
         self.epoch = int(options['-ep'])
         self.friendsFile = options['-friends'] if options.contains('-friends') else ''
+        self.netMode = options['-net'] if options.contains('-net') else ''
+        self.netSeed = int(options['-seed']) if options.contains('-seed') else 1
+        if self.netMode not in ('', 'hip'):
+            print('CUNE: -net takes the value hip.')
+            exit(-1)
 
     def _item_sets(self):
         self.PositiveSet = defaultdict(list)                    # CUNE.py:107-113
@@ -49,6 +58,9 @@ class CUNE(IterativeRecommender):
         if hasattr(self, 'IPositiveSet'):
             return
         self.IPositiveSet = defaultdict(list)
+        if not self.friendsFile and self.netMode == 'hip':
+            self._user_network()
+            return
         if not self.friendsFile:
             print('CUNE: no -friends file: the user-network stage (gensim) is not part of this build; every user takes the plain step.')
             return
@@ -59,6 +71,42 @@ class CUNE(IterativeRecommender):
             for friend in [f for f in friends.split(',') if f]:
                 if user in self.PositiveSet and friend in self.PositiveSet:      # :115-117
                     self.IPositiveSet[user] += list(set(self.PositiveSet[friend]).difference(self.PositiveSet[user]))
+
+    def _user_network(self):
+        """CUNE.py:34-114 with the four device stages: fills W (m x walkDim), topKSim and IPositiveSet.  The sets are built
+        on the host from the CSR rows (at config-3 size they are too large to materialise: out of scope)."""
+        d, rt = self.data, self.recType
+        print('Kind Note: This method will probably take much time.')
+        print('Building collaborative user network...')
+        arrays = d.to_arrays(rt)
+        m, n = d.getSize('user'), d.getSize(rt)
+        u_ptr, u_items = arrays['indptr'], arrays['indices']
+        users = np.repeat(np.arange(m, dtype=np.int32), np.diff(u_ptr))
+        i_ptr = np.concatenate([[0], np.cumsum(np.bincount(u_items, minlength=n))]).astype(np.int64)
+        dev = self._device()
+        dev.cnet_set_pairs(m, n, u_ptr, u_items, i_ptr, users[np.argsort(u_items, kind='stable')])
+        print('Generating random deep walks...')
+        self.walks = dev.cnet_walks(self.walkCount, self.walkLength, self.netSeed)
+        print('Generating user embedding...')
+        self.W = dev.cnet_embed(self.walkDim, self.winSize, self.epoch, self.netSeed)
+        print('User embedding generated.')
+        print('Constructing similarity matrix...')
+        ids, sims = dev.cnet_friends(self.topK)
+        unames, inames = d.id2name['user'], d.id2name[rt]
+        net = np.flatnonzero(ids[:, 0] >= 0)                    # a network user has at least one neighbour, hence a friend
+        self.topKSim = {}
+        for i, u in enumerate(net, 1):
+            self.topKSim[unames[u]] = [(unames[b], float(s)) for b, s in zip(ids[u], sims[u]) if b >= 0]
+            if i % 200 == 0:
+                print('progress:', i, '/', len(net))
+        print('Similarity matrix finished.')
+        print('Preparing item sets...')
+        for u in net:                                           # :112-114; a friend's new items in ascending item id
+            mine = u_items[u_ptr[u]:u_ptr[u + 1]]
+            row = self.IPositiveSet[unames[u]]
+            for b in ids[u][ids[u] >= 0]:
+                theirs = u_items[u_ptr[b]:u_ptr[b + 1]]
+                row += [inames[x] for x in theirs[~np.isin(theirs, mine)]]
 
     def buildModel(self):
         self._item_sets()
