@@ -146,8 +146,15 @@ def tables(walk_arr, m):
     return cnt, keep, cum
 
 
-def embed(walk_arr, m, dim, window, epochs, seed, negative=5, round_walks=1, dtype=np.float32, snapshots=None):
-    """syn0 [m, dim] after `epochs` epochs over the walks in the given order; snapshots: {epoch count: copy of syn0}."""
+def embed(walk_arr, m, dim, window, epochs, seed, negative=5, round_walks=1, dtype=np.float32, snapshots=None, stats=None):
+    """syn0 [m, dim] after `epochs` epochs over the walks in the given order; snapshots: {epoch count: copy of syn0}.
+    stats (a dict, filled): 'evals' logits computed, 'max_abs_f' the largest |logit|, 'cutoffs' how many had |logit| >= 6,
+    'cutoff_events' their (walk, epoch, position, d); per (epoch, walk) visit in order: 'kept' words left by subsampling,
+    'trained' positions that had a context, 'targets' distinct syn1neg rows used; where stats comes in with a list under
+    'f', every logit is appended to it in evaluation order (the order is the same for every dtype)."""
+    if stats is not None:
+        stats.update({'evals': 0, 'max_abs_f': 0.0, 'cutoffs': 0, 'cutoff_events': [], 'kept': [], 'trained': [], 'targets': []})
+        all_f = stats.get('f')
     ft = dtype
     nw, L = walk_arr.shape
     cnt, keep, cum = tables(walk_arr, m)
@@ -167,6 +174,7 @@ def embed(walk_arr, m, dim, window, epochs, seed, negative=5, round_walks=1, dty
                 kept = [p for p in range(L) if (cnet_hash(seed ^ TAG_SUB, w, ep, p, 0) >> 32) < keep[ids[p]]]
                 done = float((ep * nw + w) * L) / float(epochs * nw * L)
                 alpha = ft(np.float32(0.025 - (0.025 - 1e-4) * done))
+                trained, targets = 0, set()
                 for kp, p in enumerate(kept):
                     word = ids[p]
                     b = ((cnet_hash(seed ^ TAG_WIN, w, ep, p, 0) >> 32) * window) >> 32
@@ -174,6 +182,7 @@ def embed(walk_arr, m, dim, window, epochs, seed, negative=5, round_walks=1, dty
                     ctx = [ids[kept[c]] for c in range(lo, hi) if c != kp]
                     if not ctx:
                         continue
+                    trained += 1
                     neu1 = np.zeros(dim, ft)
                     for x in ctx:
                         neu1 = neu1 + cur0.get(x, syn0[x])
@@ -188,6 +197,15 @@ def embed(walk_arr, m, dim, window, epochs, seed, negative=5, round_walks=1, dty
                                 continue
                         row = cur1.get(tgt, syn1[tgt])
                         f = ft(np.dot(neu1, row)) if ft is np.float64 else _sum32(neu1 * row)
+                        if stats is not None:
+                            targets.add(tgt)
+                            stats['evals'] += 1
+                            stats['max_abs_f'] = max(stats['max_abs_f'], abs(float(f)))
+                            if all_f is not None:
+                                all_f.append(float(f))
+                            if f >= 6.0 or f <= -6.0:
+                                stats['cutoffs'] += 1
+                                stats['cutoff_events'].append((w, ep, p, d))
                         if f >= 6.0 or f <= -6.0:
                             continue
                         g = (ft(1.0 if d == 0 else 0.0) - one / (one + np.exp(-f))) * alpha
@@ -196,6 +214,8 @@ def embed(walk_arr, m, dim, window, epochs, seed, negative=5, round_walks=1, dty
                     work = work * inv
                     for x in ctx:
                         cur0[x] = cur0.get(x, syn0[x]) + work
+                if stats is not None:
+                    stats['kept'].append(len(kept)); stats['trained'].append(trained); stats['targets'].append(len(targets))
                 for tab, acc, M in ((cur0, acc0, syn0), (cur1, acc1, syn1)):
                     for x, row in tab.items():
                         q = np.rint((row - M[x]).astype(np.float64) * FIX).astype(np.int64)
@@ -282,3 +302,24 @@ def planted_score(ids, group):
     """Share of each user's listed friends that are in its own group, averaged over the users."""
     same = [(group[row[row >= 0]] == group[a]).mean() for a, row in enumerate(ids) if (row >= 0).any()]
     return float(np.mean(same))
+
+
+# ---- the singleton-items log of the walk edge tests (tests/test_gpu_cnet_edges.py, tests/test_cune_net_golden.py) ----
+def singleton_log():
+    """(ev_u, ev_i, m, n, marked users): item 10 has 300 listeners (users 0..299); items nobody else listens to (zero-width
+    entries of the prefix) sit at the start, at the end and as a run in the middle of network users' rows; users 300..304
+    have only such items and are outside the network."""
+    rows = {0: [0, 10, 20, 21, 22, 30, 40],       # first, a run of three in the middle, last
+            1: [1, 10, 30, 41],                   # first and last
+            2: [10, 30],
+            5: [2, 10],                           # first only
+            6: [10, 43],                          # last only
+            298: [10, 31],
+            299: [10, 23, 24, 31, 42]}            # a run of two in the middle, last
+    for u in range(300):
+        rows.setdefault(u, [10])
+    for u in range(300, 305):
+        rows[u] = [50 + u - 300]
+    ev_u = np.concatenate([[u] * len(r) for u, r in sorted(rows.items())])
+    ev_i = np.concatenate([r for _, r in sorted(rows.items())])
+    return ev_u.astype(np.int32), ev_i.astype(np.int32), 305, 55, [0, 1, 5, 6, 299]

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from helpers import numpy_cune_net as cn
-from util import gz
+from util import gj, gz
 
 
 def test_implicit_network_is_the_reference_cunet():
@@ -69,3 +69,43 @@ def test_walk_contract_takes_the_redraw_cutoff_on_a_clique():
     w = cn.walks(cn.Net(up, ui, ip, iu), 20, 10, 1, stats)
     assert w.shape == (120, 10) and stats['cutoffs'] >= 1
     assert (w[:, 1:] != w[:, :-1]).all()                              # a user is never its own neighbour
+
+
+def test_entry_rule_over_zero_width_prefix_entries():
+    """singleton_log: items nobody else listens to at the start, the end and in the middle of a user's row leave flat
+    stretches in the prefix; entry(a, r) must index the explicit list over them, for every r."""
+    ev_u, ev_i, m, n, marked = cn.singleton_log()
+    (up, ui), (ip, iu) = cn.pairs_from_events(ev_u, ev_i, m, n)
+    net = cn.Net(up, ui, ip, iu)
+    assert np.diff(ip).max() == 300 and len(net.users) == 300
+    for a in marked + [2, 150, 298]:
+        lst = net.cunet(a)
+        width = np.diff(np.concatenate([[0], net.pref[a]]))
+        assert len(lst) == net.total[a] >= 299 and (a in (2, 150, 298) or (width == 0).any())
+        assert [net.entry(a, r) for r in range(len(lst))] == lst, a
+    assert all(net.total[a] == 0 for a in range(300, 305))
+
+
+def test_embed_contract_statistics():
+    """The optional stats of cn.embed count what the walks do and leave the result alone."""
+    walks = np.random.RandomState(28).randint(0, 3, (16, 10)).astype(np.int32)
+    stats = {'f': []}
+    W = cn.embed(walks, 3, 4, 5, 2, 3, round_walks=8, dtype=np.float64, stats=stats)
+    assert np.array_equal(W, cn.embed(walks, 3, 4, 5, 2, 3, round_walks=8, dtype=np.float64))
+    kept, trained, targets = (np.array(stats[k]) for k in ('kept', 'trained', 'targets'))
+    assert len(kept) == len(trained) == len(targets) == 32
+    assert (kept == 0).any() and (kept == 1).any() and (trained[kept <= 1] == 0).all() and (trained <= kept).all() and trained.sum() > 0
+    assert (targets <= 6 * trained).all() and ((targets > 0) == (trained > 0)).all()
+    assert stats['evals'] == len(stats['f']) > 0 and stats['max_abs_f'] == np.abs(stats['f']).max() < 6
+    assert stats['cutoffs'] == 0 and stats['cutoff_events'] == []
+
+
+def test_trained_embedding_golden_meets_its_condition():
+    """g15_cune_trained (tools/make_cune_net_goldens.py --trained): logits of at least 4, none cut off, in float32 and float64."""
+    z, q = gz('g15_cune_trained.npz'), gj('g15_cune_trained.json')
+    assert z['walks'].shape == (q['nw'], q['L']) == (64, 64) and z['walks'].dtype == np.int32
+    assert z['W'].shape == (q['m'], q['dim']) == (64, 20) and z['W'].dtype == np.float64
+    assert min(q['max_abs_f'].values()) >= 4.0 and max(q['cutoffs'].values()) == 0 and q['epochs'] % 10 == 0 and q['gap'] > 0
+    assert abs(np.abs(z['W']).max() - q['max_abs_w']) < 1e-15
+    tried = gj('g15_cune_cutoff_search.json')['tried']              # the cut-off fixture: searched, none qualified (DESIGN.md section 18)
+    assert len(tried) <= 20 and not any(t['verdict'] == 'qualifies' for t in tried)
