@@ -422,6 +422,15 @@ int yue_ipf_topn(yue_ctx *ctx, const int32_t *users, int64_t nu, int N, int32_t 
  *                        The walks (user ascending, t ascending) are stored in the order of (hash(seed ^ shuffle, walk),
  *                        walk) -- shuffle(self.walks), :74 -- and stay on the device.  walks_out [nw][L] may be NULL.
  *   yue_cnet_set_walks     uploads walks of the caller's (ids below m) in training order instead.
+ *   yue_cnet_set_sentences uploads ns sentences of unequal length instead (ptr[ns + 1] from 0 to the words, ids below m; Song2vec:
+ *                        ids are tracks, a sentence is a user's play list).  yue_cnet_embed cuts every sentence into
+ *                        consecutive segments of at most S words, the last one shorter; S is the largest value <= 64 for
+ *                        which S (negative + 2) rows of dim floats fit 60 KiB (S = 64 at dim 20, 34 at dim 64, 17 at dim 128
+ *                        with 5 negatives); S < 2 window + 1 is refused.  A segment is trained as a walk of its own length:
+ *                        windows do not cross a cut (stated deviation: gensim cuts sentences at 10,000 words only).  Alpha
+ *                        runs over the words passed (the words of the segments before); counts, subsampling thresholds and
+ *                        the negative table run over the real words.  Sentences that all have one length L <= S give the
+ *                        embedding of the same rows as walks, bit for bit.
  *   yue_cnet_embed         Word2Vec(walks, size=dim, window, min_count=0, iter=epochs) as gensim documents it, with this
  *                        stream: CBOW with the mean of the context, `negative` negatives from the unigram^0.75 table of the
  *                        walks' user counts (a draw equal to the word is skipped), window shrink b uniform in [0, window)
@@ -443,9 +452,39 @@ int yue_cnet_set_pairs(yue_ctx *ctx, int64_t m, int64_t n, const int64_t *u_ptr,
                        const int32_t *i_users, int64_t nnz);
 int yue_cnet_walks(yue_ctx *ctx, int T, int L, uint64_t seed, int32_t *walks_out, int64_t *nw_out);
 int yue_cnet_set_walks(yue_ctx *ctx, int64_t m, int64_t nw, int L, const int32_t *walks);
+int yue_cnet_set_sentences(yue_ctx *ctx, int64_t m, int64_t ns, const int64_t *ptr, const int32_t *ids);
 int yue_cnet_embed(yue_ctx *ctx, int dim, int window, int epochs, int negative, int64_t round_walks, uint64_t seed, float *W_out);
 int yue_cnet_set_embedding(yue_ctx *ctx, int64_t m, int dim, const float *W, const int32_t *users, int64_t nu);
 int yue_cnet_friends(yue_ctx *ctx, int K, int32_t *friends_out, double *sims_out);
+
+/*
+ * Song2vec's iteration (reference recommender/advanced/Song2vec.py:162-189) -- a biased matrix factorisation by sequential
+ * SGD over (user, item, count) steps, then a similarity regulariser over (track, similar track) pairs.  The factors are
+ * X = P (users), Y = Q (items) of yue_set_factors (float32, k <= 128); the embedding and the similar tracks come from
+ * yue_cnet_set_sentences / yue_cnet_embed / yue_cnet_friends.  Contract: tests/helpers/numpy_song2vec.py, DESIGN.md 19.
+ *   yue_s2v_set_state / yue_s2v_get_state   the biases Bu [m], Bi [n], fp64.
+ *   yue_s2v_set_steps   the rating steps in the reference's order (users in id order, a user's items in first-listen order,
+ *                       count = the user's events of the item).  A user's steps must be contiguous, otherwise the call is
+ *                       refused: the reference reads bu = Bu[u] once per user, and every step of the user uses that value in
+ *                       its regulariser.  Builds the dependency schedule.
+ *   yue_s2v_set_pairs   the similarity pairs in visiting order, sim in fp64 (rounded to float32 where NumPy rounds it: it
+ *                       meets a float32 dot).  t1 == t2 is refused.  Builds the dependency schedule.
+ *   yue_s2v_epoch       one iteration: the rating pass, then the pair pass (the arithmetic, call by call as NumPy 2 rounds
+ *                       it: csrc/s2v_kernels.hpp).  err2_steps [T] and err2_pairs [Pn] (either may be NULL) take the squared
+ *                       error of every step and pair, so that the caller adds them in the reference's order and composes the
+ *                       loss of :190 itself.
+ * Schedule: level(step) = 1 + max(level of the previous step of the same user, ... of the same item); for pairs, of either
+ * track.  Two steps of a level share no row and every step finds what the sequential loop would hand it, so one launch per
+ * level with one wave per step gives the sequential loop's result bit for bit, without atomics.  Option "s2v_schedule":
+ * 1 = levels (default), 0 = one wave walks all steps in order in one launch (the yardstick).  Read-only options
+ * "s2v_levels_steps", "s2v_levels_pairs" (launches per pass) and "s2v_last_ns" (device time of the last yue_s2v_epoch).
+ */
+int yue_s2v_set_state(yue_ctx *ctx, const double *Bu, const double *Bi);
+int yue_s2v_get_state(yue_ctx *ctx, double *Bu, double *Bi);
+int yue_s2v_set_steps(yue_ctx *ctx, const int32_t *u, const int32_t *i, const int32_t *count, int64_t T);
+int yue_s2v_set_pairs(yue_ctx *ctx, const int32_t *t1, const int32_t *t2, const double *sim, int64_t Pn);
+int yue_s2v_epoch(yue_ctx *ctx, double lr, double regU, double regI, double regB, double alpha, double globalMean, double *err2_steps,
+                  double *err2_pairs);
 
 /* Multi-GPU (one process per GPU, RCCL over xGMI).  Rank 0 creates the id, the caller ships
  * the 128 bytes to the other ranks (any side channel), every rank calls yue_comm_init. */

@@ -30,7 +30,9 @@ SYMBOLS = ['yue_last_error', 'yue_version', 'yue_ctx_create', 'yue_ctx_destroy',
            'yue_cof_cooccur', 'yue_cof_get_cooccur', 'yue_cof_set_sppmi', 'yue_cof_set_state', 'yue_cof_get_state', 'yue_cof_item_sweep',
            'yue_knn_set_pairs', 'yue_knn_neighbors', 'yue_knn_predict', 'yue_knn_topn',
            'yue_ipf_set_graph', 'yue_ipf_predict', 'yue_ipf_topn',
-           'yue_cnet_set_pairs', 'yue_cnet_walks', 'yue_cnet_set_walks', 'yue_cnet_embed', 'yue_cnet_set_embedding', 'yue_cnet_friends']
+           'yue_cnet_set_pairs', 'yue_cnet_walks', 'yue_cnet_set_walks', 'yue_cnet_set_sentences', 'yue_cnet_embed', 'yue_cnet_set_embedding',
+           'yue_cnet_friends',
+           'yue_s2v_set_state', 'yue_s2v_get_state', 'yue_s2v_set_steps', 'yue_s2v_set_pairs', 'yue_s2v_epoch']
 
 
 class YueHipError(RuntimeError):
@@ -533,6 +535,42 @@ class Device(object):
         return ids, scores, lens
 
     # -- CUNE's user-network stage (needs no factors) --------------------------------------------
+    # -- Song2vec ---------------------------------------------------------------------------
+    def s2v_set_state(self, Bu, Bi):
+        Bu, a = _f64(Bu)
+        Bi, b = _f64(Bi)
+        assert Bu.shape == (self.m,) and Bi.shape == (self.n,), 's2v_set_state: Bu [m], Bi [n]'
+        self._chk(self._lib.yue_s2v_set_state(self._ctx, a, b))
+
+    def s2v_get_state(self):
+        Bu, Bi = np.empty(self.m, np.float64), np.empty(self.n, np.float64)
+        self._chk(self._lib.yue_s2v_get_state(self._ctx, Bu.ctypes.data_as(C.POINTER(C.c_double)), Bi.ctypes.data_as(C.POINTER(C.c_double))))
+        return Bu, Bi
+
+    def s2v_set_steps(self, u, i, count):
+        u, a = _i32(u)
+        i, b = _i32(i)
+        count, d = _i32(count)
+        assert len(u) == len(i) == len(count), 's2v_set_steps: u, i and count must hold one entry per step'
+        self._s2v_T = len(u)
+        self._chk(self._lib.yue_s2v_set_steps(self._ctx, a, b, d, C.c_int64(len(u))))
+
+    def s2v_set_pairs(self, t1, t2, sim):
+        t1, a = _i32(t1)
+        t2, b = _i32(t2)
+        sim, d = _f64(sim)
+        assert len(t1) == len(t2) == len(sim), 's2v_set_pairs: t1, t2 and sim must hold one entry per pair'
+        self._s2v_P = len(t1)
+        self._chk(self._lib.yue_s2v_set_pairs(self._ctx, a, b, d, C.c_int64(len(t1))))
+
+    def s2v_epoch(self, lr, regU, regI, regB, alpha, globalMean=0.0):
+        """One iteration of Song2vec.py:163-189.  Returns the squared errors per step and per pair (float64)."""
+        e1 = np.zeros(getattr(self, '_s2v_T', 0), np.float64)
+        e2 = np.zeros(getattr(self, '_s2v_P', 0), np.float64)
+        self._chk(self._lib.yue_s2v_epoch(self._ctx, C.c_double(lr), C.c_double(regU), C.c_double(regI), C.c_double(regB), C.c_double(alpha),
+                                          C.c_double(globalMean), e1.ctypes.data_as(C.POINTER(C.c_double)), e2.ctypes.data_as(C.POINTER(C.c_double))))
+        return e1, e2
+
     def cnet_set_pairs(self, m, n, u_ptr, u_items, i_ptr, i_users):
         """Distinct pairs both ways: user-major (items ascending) and item-major (users ascending)."""
         u_ptr, a = _i64(u_ptr)
@@ -556,6 +594,14 @@ class Device(object):
         walks, p = _i32(walks)
         assert walks.ndim == 2
         self._chk(self._lib.yue_cnet_set_walks(self._ctx, C.c_int64(m), C.c_int64(walks.shape[0]), C.c_int(walks.shape[1]), p))
+        self.cnet_m = int(m)
+
+    def cnet_set_sentences(self, m, ptr, ids):
+        """Sentences of unequal length (ids below m; ptr [ns + 1]); cnet_embed cuts them into segments."""
+        ptr, a = _i64(ptr)
+        ids, b = _i32(ids)
+        assert len(ptr) >= 2 and int(ptr[-1]) == len(ids), 'cnet_set_sentences: the pointer must run from 0 to the number of words'
+        self._chk(self._lib.yue_cnet_set_sentences(self._ctx, C.c_int64(m), C.c_int64(len(ptr) - 1), a, b))
         self.cnet_m = int(m)
 
     def cnet_embed(self, dim, window, epochs, seed, negative=5, round_walks=0):

@@ -18,6 +18,13 @@ struct yue_cnet {
     int64_t wm = 0, nw = 0;                      // wm: users the walk ids are below
     int L = 0;
     DevBuf<int32_t> walks, cnt, list, list_n, net, friends;
+    // sentences of unequal length (yue_cnet_set_sentences), kept on the host: yue_cnet_embed cuts them into segments
+    // once it knows dim and negative
+    bool sent = false;
+    std::vector<int64_t> s_ptr;
+    std::vector<int32_t> s_ids;
+    DevBuf<int32_t> seg_len;
+    DevBuf<int64_t> seg_pre;
     // embedding
     int64_t em = 0, nnet = 0;                    // em == 0: none
     int dim = 0;
@@ -37,6 +44,7 @@ void cnet_release(yue_ctx *c) {
     if (!k) return;
     k->u_ptr.release(); k->i_ptr.release(); k->pref.release(); k->total.release(); k->dest.release(); k->u_items.release(); k->i_users.release();
     k->walks.release(); k->cnt.release(); k->list.release(); k->list_n.release(); k->net.release(); k->friends.release();
+    k->seg_len.release(); k->seg_pre.release();
     k->syn0.release(); k->syn1.release(); k->acc0.release(); k->acc1.release(); k->flag0.release(); k->flag1.release();
     k->keep.release(); k->cum.release(); k->norm.release(); k->sims.release();
     for (auto &e : k->ev) if (e) (void)hipEventDestroy(e);
@@ -100,7 +108,7 @@ int stop_clock(yue_ctx *c, yue_cnet *k) {
 }
 
 // the walks on the device changed: whatever was trained on the old ones is gone
-void new_walks(yue_cnet *k, int64_t wm, int64_t nw, int L) { k->wm = wm; k->nw = nw; k->L = L; k->em = 0; }
+void new_walks(yue_cnet *k, int64_t wm, int64_t nw, int L) { k->wm = wm; k->nw = nw; k->L = L; k->em = 0; k->sent = false; }
 
 }  // namespace
 
@@ -196,16 +204,59 @@ int yue_cnet_set_walks(yue_ctx *c, int64_t m, int64_t nw, int L, const int32_t *
     return YUE_OK;
 }
 
+int yue_cnet_set_sentences(yue_ctx *c, int64_t m, int64_t ns, const int64_t *ptr, const int32_t *ids) {
+    if (!c) return fail(YUE_ERR_ARG, "yue_cnet_set_sentences: null context");
+    if (m < 1 || m >= INT32_MAX || ns < 1 || !ptr || ptr[0] != 0 || ptr[ns] < 1 || ptr[ns] >= INT32_MAX || !ids)
+        return fail(YUE_ERR_ARG, "yue_cnet_set_sentences: need 1 <= m < 2^31 - 1, ns >= 1, a pointer from 0 to the words, 1 <= words < 2^31 - 1");
+    for (int64_t q = 0; q < ns; ++q)
+        if (ptr[q + 1] < ptr[q]) return fail(YUE_ERR_ARG, "yue_cnet_set_sentences: the pointer must be non-decreasing");
+    for (int64_t e = 0; e < ptr[ns]; ++e)
+        if (ids[e] < 0 || ids[e] >= m) return fail(YUE_ERR_ARG, "yue_cnet_set_sentences: id out of range");
+    HIPCHK(hipSetDevice(c->device));
+    yue_cnet *k = nullptr;
+    int rc = cnet_state(c, &k);
+    if (rc) return rc;
+    new_walks(k, m, 0, 0);
+    k->s_ptr.assign(ptr, ptr + ns + 1);
+    k->s_ids.assign(ids, ids + ptr[ns]);
+    k->sent = true;
+    return YUE_OK;
+}
+
 int yue_cnet_embed(yue_ctx *c, int dim, int window, int epochs, int negative, int64_t round_walks, uint64_t seed, float *W_out) {
     if (!c) return fail(YUE_ERR_ARG, "yue_cnet_embed: null context");
     yue_cnet *k = c->cnet;
-    if (!k || k->nw == 0) return fail(YUE_ERR_ARG, "yue_cnet_embed: call yue_cnet_walks or yue_cnet_set_walks first");
+    if (!k || (k->nw == 0 && !k->sent)) return fail(YUE_ERR_ARG, "yue_cnet_embed: call yue_cnet_walks or yue_cnet_set_walks first (or yue_cnet_set_sentences)");
     if (dim < 1 || dim > yue::kCnetMaxDim || window < 1 || epochs < 1 || negative < 0 || negative > 64 || round_walks < 0)
         return fail(YUE_ERR_ARG, "yue_cnet_embed: need 1 <= dim <= 128, window >= 1, epochs >= 1, 0 <= negative <= 64, round_walks >= 0");
-    const int64_t m = k->wm, nw = k->nw;
+    const int64_t m = k->wm;
+    const bool sent = k->sent;
+    const auto lds_of = [&](int len) { return (size_t)len * (negative + 2) * dim * sizeof(float) + (size_t)len * (negative + 1) * sizeof(int32_t); };
+    std::vector<int32_t> seg_ids, seg_len;
+    std::vector<int64_t> seg_pre;
+    if (sent) {
+        // segments of at most S words: the largest S <= 64 whose S (negative + 2) rows of dim floats fit 60 KiB (and, with
+        // the target ids behind them, the workgroup's LDS); windows do not cross a cut
+        int S = yue::kCnetMaxL;
+        while (S > 0 && ((size_t)S * (negative + 2) * dim * sizeof(float) > (size_t)yue::kCnetEmbedLds || lds_of(S) > (size_t)yue::kCnetSegmentLds)) --S;
+        if (S < 2 * window + 1)
+            return fail(YUE_ERR_ARG, "yue_cnet_embed: a segment holds " + std::to_string(S) + " words at this dim and negative, fewer than 2 window + 1");
+        const int64_t ns = (int64_t)k->s_ptr.size() - 1;
+        for (int64_t q = 0; q < ns; ++q)
+            for (int64_t b = k->s_ptr[(size_t)q]; b < k->s_ptr[(size_t)q + 1]; b += S) {
+                const int64_t e = std::min<int64_t>(b + S, k->s_ptr[(size_t)q + 1]);
+                seg_pre.push_back(b);                      // the words passed: a prefix of the lengths
+                seg_len.push_back((int32_t)(e - b));
+                seg_ids.insert(seg_ids.end(), k->s_ids.begin() + b, k->s_ids.begin() + e);
+                seg_ids.resize(seg_len.size() * (size_t)S, 0);
+            }
+        if ((int64_t)seg_ids.size() >= INT32_MAX) return fail(YUE_ERR_ARG, "yue_cnet_embed: more than 2^31 segment entries");
+        k->nw = (int64_t)seg_len.size(); k->L = S;
+    }
+    const int64_t nw = k->nw;
     const int L = k->L, rows = L * (negative + 2);
-    const size_t lds = (size_t)rows * dim * sizeof(float) + (size_t)L * (negative + 1) * sizeof(int32_t);
-    if (lds > (size_t)yue::kCnetEmbedLds)
+    const size_t lds = lds_of(L);
+    if (!sent && lds > (size_t)yue::kCnetEmbedLds)
         return fail(YUE_ERR_ARG, "yue_cnet_embed: L (negative + 2) rows of dim floats must fit 60 KiB of LDS (a walk's working rows)");
     if (m * dim >= ((int64_t)1 << 40)) return fail(YUE_ERR_ARG, "yue_cnet_embed: m dim is too large");
     if (round_walks == 0) round_walks = kDefaultRoundWalks;
@@ -222,8 +273,13 @@ int yue_cnet_embed(yue_ctx *c, int dim, int window, int epochs, int negative, in
     HIPCHK(hipMemsetAsync(k->acc1.p, 0, cells * sizeof(long long), c->stream));
     HIPCHK(hipMemsetAsync(k->flag0.p, 0, (size_t)m * sizeof(int), c->stream));
     HIPCHK(hipMemsetAsync(k->flag1.p, 0, (size_t)m * sizeof(int), c->stream));
-    const int64_t words = nw * L;
-    hipLaunchKernelGGL(yue::k_cnet_count, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, c->stream, k->walks.p, words, k->cnt.p);
+    const int64_t words = sent ? (int64_t)k->s_ids.size() : nw * L;
+    if (sent) {
+        int rcs;
+        if ((rcs = upload(k->walks, seg_ids.data(), nw * L)) || (rcs = upload(k->seg_len, seg_len.data(), nw)) || (rcs = upload(k->seg_pre, seg_pre.data(), nw))) return rcs;
+        hipLaunchKernelGGL(yue::k_sent_count, dim3((unsigned)((nw * L + 255) / 256)), dim3(256), 0, c->stream, k->walks.p, k->seg_len.p, nw * L, L, k->cnt.p);
+    } else
+        hipLaunchKernelGGL(yue::k_cnet_count, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, c->stream, k->walks.p, words, k->cnt.p);
     HIPCHK(hipGetLastError());
     std::vector<int32_t> cnt((size_t)m);
     HIPCHK(hipMemcpyAsync(cnt.data(), k->cnt.p, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
@@ -256,6 +312,7 @@ int yue_cnet_embed(yue_ctx *c, int dim, int window, int epochs, int negative, in
     a.m = m; a.nw = nw; a.walks = k->walks.p; a.cnt = k->cnt.p; a.keep = k->keep.p; a.cum = k->cum.p;
     a.syn0 = k->syn0.p; a.syn1 = k->syn1.p; a.acc0 = k->acc0.p; a.acc1 = k->acc1.p; a.flag0 = k->flag0.p; a.flag1 = k->flag1.p;
     a.list = k->list.p; a.list_n = k->list_n.p;
+    if (sent) { a.len = k->seg_len.p; a.wpre = k->seg_pre.p; a.words = words; }
     a.L = L; a.dim = dim; a.window = window; a.negative = negative; a.epochs = epochs; a.seed = seed;
     HIPCHK(hipEventRecord(k->ev[0], c->stream));
     hipLaunchKernelGGL(yue::k_cnet_embed_init, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, c->stream, a);
@@ -263,7 +320,10 @@ int yue_cnet_embed(yue_ctx *c, int dim, int window, int epochs, int negative, in
     for (int ep = 0; ep < epochs; ++ep)
         for (int64_t w0 = 0; w0 < nw; w0 += round_walks) {
             a.epoch = ep; a.w_begin = w0; a.w_count = std::min(round_walks, nw - w0);
-            if (dim <= 64) hipLaunchKernelGGL(yue::k_cnet_embed_round<1>, dim3((unsigned)a.w_count), dim3(64), lds, c->stream, a);
+            if (sent) {
+                if (dim <= 64) hipLaunchKernelGGL(yue::k_sent_embed_round<1>, dim3((unsigned)a.w_count), dim3(64), lds, c->stream, a);
+                else hipLaunchKernelGGL(yue::k_sent_embed_round<2>, dim3((unsigned)a.w_count), dim3(64), lds, c->stream, a);
+            } else if (dim <= 64) hipLaunchKernelGGL(yue::k_cnet_embed_round<1>, dim3((unsigned)a.w_count), dim3(64), lds, c->stream, a);
             else hipLaunchKernelGGL(yue::k_cnet_embed_round<2>, dim3((unsigned)a.w_count), dim3(64), lds, c->stream, a);
             hipLaunchKernelGGL(yue::k_cnet_embed_apply, dim3((unsigned)a.w_count), dim3(64), 0, c->stream, a);
         }

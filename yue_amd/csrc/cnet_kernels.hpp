@@ -27,6 +27,7 @@ constexpr int kCnetMaxK = 100;
 constexpr int kCnetMaxVisited = 15360;     // T * (L - 1) ids of visited[start] in LDS (60 KiB)
 constexpr int kCnetRedraws = 10;           // CUNE.py:64-69
 constexpr int kCnetEmbedLds = 60 * 1024;   // working rows of one walk
+constexpr int kCnetSegmentLds = 63 * 1024; // ... of one segment of a sentence, with the ids of its targets (64 KiB less the static arrays)
 constexpr double kCnetFix = 68719476736.0;         // 2^36: fixed-point scale of the round's row differences
 constexpr double kCnetUnfix = 1.0 / 68719476736.0;
 constexpr float kCnetMaxExp = 6.0f;
@@ -126,6 +127,12 @@ __global__ void k_cnet_count(const int32_t *walks, int64_t words, int32_t *cnt) 
     if (e < words) atomicAdd(&cnt[walks[e]], 1);
 }
 
+// ... over segments of unequal length (yue_cnet_set_sentences): entry e of the [nw][L] array counts where it is a real word
+__global__ void k_sent_count(const int32_t *walks, const int32_t *len, int64_t entries, int L, int32_t *cnt) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < entries && (int)(e % L) < len[e / L]) atomicAdd(&cnt[walks[e]], 1);
+}
+
 struct CnetEmbedArgs {
     int64_t m, nw;
     const int32_t *walks;      // [nw][L] in training order
@@ -140,6 +147,10 @@ struct CnetEmbedArgs {
     int L, dim, window, negative, epochs, epoch;
     int64_t w_begin, w_count;
     uint64_t seed;
+    // behind what the walks use, so that their kernels read their arguments where they did
+    const int32_t *len;        // sentences only: [nw] words of the segment (<= L; the rest of its row is padding)
+    const int64_t *wpre;       // sentences only: [nw] words of the segments before it
+    int64_t words;             // sentences only: all words
 };
 
 __global__ void k_cnet_embed_init(CnetEmbedArgs a) {
@@ -157,9 +168,10 @@ __global__ void k_cnet_embed_init(CnetEmbedArgs a) {
 
 // One wave per walk of the round.  Lane l holds elements l (+ 64) of every vector.  LDS: cur0[L][dim] the syn0 rows of
 // the walk's users (slot = first position of the user), cur1[L * (negative + 1)][dim] the syn1neg rows of its targets in
-// first-use order, ids1 their ids.
-template <int KR>
-__global__ __launch_bounds__(64) void k_cnet_embed_round(CnetEmbedArgs a) {
+// first-use order, ids1 their ids.  VAR (sentences cut into segments, yue_cnet_set_sentences): the walk is a segment of
+// len[w] <= L words -- lanes and positions beyond it take no part, and alpha runs over the words passed, not over w L.
+template <int KR, bool VAR>
+__device__ __forceinline__ void cnet_embed_round_body(const CnetEmbedArgs &a) {
     extern __shared__ float lds[];
     __shared__ int32_t sid[kCnetMaxL], sslot[kCnetMaxL], fpos[kCnetMaxL];
     const int lane = threadIdx.x;
@@ -169,16 +181,17 @@ __global__ __launch_bounds__(64) void k_cnet_embed_round(CnetEmbedArgs a) {
     int32_t *ids1 = (int32_t *)(cur1 + (size_t)rows1 * dim);
     const int64_t w = a.w_begin + blockIdx.x;
     const uint64_t ew = (uint64_t)a.epoch;
+    const int Lw = VAR ? a.len[w] : L;
 
     int32_t id = 0;
     bool keep = false;
-    if (lane < L) {
+    if (lane < Lw) {
         id = a.walks[w * L + lane];
         sid[lane] = id;
         keep = (cnet_hash(a.seed ^ kCnetTagSub, (uint64_t)w, ew, (uint64_t)lane, 0) >> 32) < a.keep[id];
     }
     __syncthreads();
-    if (lane < L) {
+    if (lane < Lw) {
         int s = lane;
         for (int q = lane - 1; q >= 0; --q) if (sid[q] == id) s = q;
         sslot[lane] = s;
@@ -187,7 +200,7 @@ __global__ __launch_bounds__(64) void k_cnet_embed_round(CnetEmbedArgs a) {
     const int nk = __popcll(kmask);
     if (keep) fpos[__popcll(kmask & ((1ull << lane) - 1ull))] = lane;
     __syncthreads();
-    for (int p = 0; p < L; ++p)
+    for (int p = 0; p < Lw; ++p)
         if (sslot[p] == p)
             for (int r = 0; r < KR; ++r) {
                 const int e = lane + 64 * r;
@@ -195,7 +208,8 @@ __global__ __launch_bounds__(64) void k_cnet_embed_round(CnetEmbedArgs a) {
             }
     unsigned long long mod0 = 0ull;                    // slots of cur0 that were changed
     int n1 = 0;
-    const double done = (double)(((int64_t)a.epoch * a.nw + w) * L) / (double)((int64_t)a.epochs * a.nw * L);
+    const double done = VAR ? (double)((int64_t)a.epoch * a.words + a.wpre[w]) / (double)((int64_t)a.epochs * a.words)
+                            : (double)(((int64_t)a.epoch * a.nw + w) * L) / (double)((int64_t)a.epochs * a.nw * L);
     const float alpha = (float)(0.025 - (0.025 - 1e-4) * done);
 
     for (int kp = 0; kp < nk; ++kp) {
@@ -275,7 +289,7 @@ __global__ __launch_bounds__(64) void k_cnet_embed_round(CnetEmbedArgs a) {
     // the walk's differences against the round-start rows, in fixed point
     int32_t *list = a.list + (int64_t)blockIdx.x * (L + rows1);
     int nl = 0;
-    for (int p = 0; p < L; ++p) {
+    for (int p = 0; p < Lw; ++p) {
         if (!((mod0 >> p) & 1ull)) continue;
         const int64_t row = sid[p];
         for (int r = 0; r < KR; ++r) {
@@ -302,6 +316,12 @@ __global__ __launch_bounds__(64) void k_cnet_embed_round(CnetEmbedArgs a) {
     }
     if (lane == 0) a.list_n[blockIdx.x] = nl;
 }
+
+template <int KR>
+__global__ __launch_bounds__(64) void k_cnet_embed_round(CnetEmbedArgs a) { cnet_embed_round_body<KR, false>(a); }
+// ... of a round of segments (yue_cnet_set_sentences)
+template <int KR>
+__global__ __launch_bounds__(64) void k_sent_embed_round(CnetEmbedArgs a) { cnet_embed_round_body<KR, true>(a); }
 
 // One wave per walk of the finished round: every flagged row is applied once (whichever wave clears the flag first; the
 // value does not depend on which): row = fp32(fp64(row) + sum * 2^-36), sum = 0.

@@ -7,7 +7,8 @@
 //   wrmf_host.hip   WRMF (ALS half-sweeps)                     knn_host.hip   UserKNN (neighbours, ranking)
 //   ipf_host.hip    IPF (session-graph ranking)                expo_host.hip  ExpoMF (exposure-weighted ALS, MFMA Gram)
 //   cof_host.hip    CoFactor (co-occurrence, level-scheduled item sweep)
-//   cnet_host.hip   CUNE's user-network stage (walks, embedding, friends)
+//   cnet_host.hip   CUNE's user-network stage (walks, embedding, friends); Song2vec's track embedding (sentences)
+//   s2v_host.hip    Song2vec's iteration (level-scheduled rating steps and similarity pairs)
 #pragma once
 #include "../../include/yue_hip.h"
 
@@ -28,6 +29,7 @@ struct yue_knn;                                      // knn_host.hip: pair lists
 struct yue_expo;                                     // expo_host.hip: mu, Gram workspace, partial sums of ExpoMF
 struct yue_cof;                                      // cof_host.hip: co-occurrence CSR, SPPMI, level schedule, G / w / c of CoFactor
 struct yue_cnet;                                     // cnet_host.hip: pairs, walks, embedding, friends of CUNE's user-network stage
+struct yue_s2v;                                      // s2v_host.hip: biases, steps, pairs and their level schedules of Song2vec's iteration
 struct yue_ipf;                                      // ipf_host.hip: session temporal graph, weights, per-slot work arrays of IPF
 
 namespace yue_host {
@@ -212,6 +214,7 @@ struct yue_ctx {
     yue_expo *expo = nullptr;            // ExpoMF state (yue_expo_set_mu), owned by expo_host.hip
     yue_cof *cof = nullptr;              // CoFactor state (yue_cof_*), owned by cof_host.hip
     yue_cnet *cnet = nullptr;            // CUNE user-network state (yue_cnet_*), owned by cnet_host.hip
+    yue_s2v *s2v = nullptr;              // Song2vec state (yue_s2v_*), owned by s2v_host.hip
 };
 
 namespace yue_host {
@@ -264,4 +267,8 @@ int cof_get_option(yue_ctx *c, const std::string &key, int64_t *value);
 void cnet_release(yue_ctx *c);
 int cnet_set_option(yue_ctx *c, const std::string &key, int64_t value);
 int cnet_get_option(yue_ctx *c, const std::string &key, int64_t *value);
+// s2v_host.hip: frees the Song2vec state; options "s2v_*"
+void s2v_release(yue_ctx *c);
+int s2v_set_option(yue_ctx *c, const std::string &key, int64_t value);
+int s2v_get_option(yue_ctx *c, const std::string &key, int64_t *value);
 }  // namespace yue_host

@@ -1,5 +1,5 @@
 // libyue_hip.so -- yue_get_option / yue_set_option (include/yue_hip.h): one table row per option of the context, walked by
-// both entry points.  The subsystems with a state of their own (wrmf_, knn_, ipf_, expo_, cof_, cnet_) keep their options and are
+// both entry points.  The subsystems with a state of their own (wrmf_, knn_, ipf_, expo_, cof_, cnet_, s2v_) keep their options and are
 // routed by prefix.  No kernel header is included: this unit holds no device code.
 #include "host_common.hpp"
 
@@ -139,6 +139,7 @@ int yue_get_option(yue_ctx *c, const char *name, int64_t *value) {
     if (key.compare(0, 5, "expo_") == 0) return yue_host::expo_get_option(c, key, value);
     if (key.compare(0, 4, "cof_") == 0) return yue_host::cof_get_option(c, key, value);
     if (key.compare(0, 5, "cnet_") == 0) return yue_host::cnet_get_option(c, key, value);
+    if (key.compare(0, 4, "s2v_") == 0) return yue_host::s2v_get_option(c, key, value);
     return fail(YUE_ERR_ARG, "yue_get_option: unknown option " + key);
 }
 
@@ -153,6 +154,7 @@ int yue_set_option(yue_ctx *c, const char *name, int64_t value) {
     if (key.compare(0, 5, "expo_") == 0) return yue_host::expo_set_option(c, key, value);
     if (key.compare(0, 4, "cof_") == 0) return yue_host::cof_set_option(c, key, value);
     if (key.compare(0, 5, "cnet_") == 0) return yue_host::cnet_set_option(c, key, value);
+    if (key.compare(0, 4, "s2v_") == 0) return yue_host::s2v_set_option(c, key, value);
     return fail(YUE_ERR_ARG, "yue_set_option: unknown option " + key);
 }
 
