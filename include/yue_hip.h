@@ -83,6 +83,8 @@ int yue_bpr_replay(yue_ctx *ctx, const int32_t *u, const int32_t *i, const int32
  * yue_adam_reset clears the moments (also done implicitly when the factor shapes change).  PARITY UNPINNED: no TensorFlow
  * here; the checker is oracle/numpy_adam.py, a restatement of the graph as written. */
 int yue_adam_reset(yue_ctx *ctx);
+/* The moments of the uploaded factors' Adam state, [m][k] / [n][k] float32 each (any may be NULL). */
+int yue_adam_get_moments(yue_ctx *ctx, float *mU, float *vU, float *mV, float *vV);
 int yue_adam_step(yue_ctx *ctx, const int32_t *u, const int32_t *i, const int32_t *j, int64_t T,
                   double lr, double reg, int64_t step, double *loss_out);
 
@@ -485,6 +487,33 @@ int yue_s2v_set_steps(yue_ctx *ctx, const int32_t *u, const int32_t *i, const in
 int yue_s2v_set_pairs(yue_ctx *ctx, const int32_t *t1, const int32_t *t2, const double *sim, int64_t Pn);
 int yue_s2v_epoch(yue_ctx *ctx, double lr, double regU, double regI, double regB, double alpha, double globalMean, double *err2_steps,
                   double *err2_pairs);
+
+/*
+ * LightGCN (reference recommender/advanced/LightGCN.py) -- embeddings propagated over the user-item graph, trained by Adam on
+ * a pairwise loss.  U = P, V = Q of yue_set_factors (float32, k <= 128); Adam's moments are those of yue_adam_step
+ * (yue_adam_reset clears them).  Contract: tests/helpers/numpy_lightgcn.py, DESIGN.md 20.  Parity with TensorFlow unpinned.
+ *   A  [(m + n)^2], symmetric: A[u][m + i] = A[m + i][u] = the pair's weight (the reference's is the squared event count).
+ *   E_0 = [U; V], E_l = A E_{l-1}, F = E_0 + sum_{l = 1..layers} E_l * rsqrt(max(|E_l row|^2, 1e-12)).
+ *   loss = sum_t -log sigmoid(F_u.F_i - F_u.F_j) + reg / 2 (|F_u|^2 + |F_i|^2 + |F_j|^2) over the T triplets.
+ *   yue_lgcn_set_graph   both sides of the pair list: u_ptr [m + 1] / u_items / u_w and i_ptr [n + 1] / i_users / i_w, ids sorted
+ *                        and unique within a row.  Ids, order and symmetry (same pairs, same weights) are checked before
+ *                        anything is stored; a refused call leaves the previous graph in place.
+ *   yue_lgcn_propagate   raw_layers_out [layers][m + n][k] (E_1 .. E_layers, may be NULL), F_out [m + n][k] (may be NULL).
+ *   yue_lgcn_grad        loss and dLoss / dU [m][k], dLoss / dV [n][k] of one minibatch, no step (outputs may be NULL).
+ *   yue_lgcn_step        the same, then dense Adam (beta 0.9 / 0.999, eps 1e-8, lr_t of `step` = 1, 2, ...) on U and V.
+ * Refused with YUE_ERR_ARG: k > 128, layers < 1 (or > 64), T < 1, an id out of range, no graph, a graph set for another m, n.
+ * Every sum has a fixed order and no atomic is used: two calls on the same input return the same bits.  Option "lgcn_hub"
+ * (default 1024): rows with more neighbours are cut into parts of that many, one wave per part, combined in ascending order.
+ * Read-only options "lgcn_last_hubs", "lgcn_last_parts", "lgcn_last_forward_ns", "lgcn_last_batch_ns",
+ * "lgcn_last_backward_ns", "lgcn_last_adam_ns" (device time of the last call's phases).
+ */
+int yue_lgcn_set_graph(yue_ctx *ctx, int64_t m, int64_t n, const int64_t *u_ptr, const int32_t *u_items, const float *u_w, const int64_t *i_ptr,
+                       const int32_t *i_users, const float *i_w);
+int yue_lgcn_propagate(yue_ctx *ctx, int layers, float *raw_layers_out, float *F_out);
+int yue_lgcn_grad(yue_ctx *ctx, int layers, const int32_t *u, const int32_t *i, const int32_t *j, int64_t T, double reg, double *loss_out,
+                  float *gU_out, float *gV_out);
+int yue_lgcn_step(yue_ctx *ctx, int layers, const int32_t *u, const int32_t *i, const int32_t *j, int64_t T, double lr, double reg, int64_t step,
+                  double *loss_out);
 
 /* Multi-GPU (one process per GPU, RCCL over xGMI).  Rank 0 creates the id, the caller ships
  * the 128 bytes to the other ranks (any side channel), every rank calls yue_comm_init. */

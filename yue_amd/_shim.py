@@ -20,7 +20,7 @@ UNIQUE_ID_BYTES = 128
 # every symbol include/yue_hip.h declares (checked by tests/test_abi.py)
 SYMBOLS = ['yue_last_error', 'yue_version', 'yue_ctx_create', 'yue_ctx_destroy', 'yue_sync',
            'yue_set_factors', 'yue_get_factors', 'yue_set_interactions', 'yue_bpr_replay',
-           'yue_bpr_rounds', 'yue_bpr_epoch', 'yue_cune_steps', 'yue_adam_reset', 'yue_adam_step', 'yue_sample_negatives', 'yue_sumsq', 'yue_scores',
+           'yue_bpr_rounds', 'yue_bpr_epoch', 'yue_cune_steps', 'yue_adam_reset', 'yue_adam_get_moments', 'yue_adam_step', 'yue_sample_negatives', 'yue_sumsq', 'yue_scores',
            'yue_topn_scan', 'yue_set_kernel_timing', 'yue_get_kernel_timing', 'yue_get_scan_stats', 'yue_get_scan_work', 'yue_set_option', 'yue_get_option',
            'yue_comm_unique_id', 'yue_comm_init', 'yue_allreduce_f64', 'yue_get_comm_stats',
            'yue_default_round_events', 'yue_epoch_plan',
@@ -32,7 +32,8 @@ SYMBOLS = ['yue_last_error', 'yue_version', 'yue_ctx_create', 'yue_ctx_destroy',
            'yue_ipf_set_graph', 'yue_ipf_predict', 'yue_ipf_topn',
            'yue_cnet_set_pairs', 'yue_cnet_walks', 'yue_cnet_set_walks', 'yue_cnet_set_sentences', 'yue_cnet_embed', 'yue_cnet_set_embedding',
            'yue_cnet_friends',
-           'yue_s2v_set_state', 'yue_s2v_get_state', 'yue_s2v_set_steps', 'yue_s2v_set_pairs', 'yue_s2v_epoch']
+           'yue_s2v_set_state', 'yue_s2v_get_state', 'yue_s2v_set_steps', 'yue_s2v_set_pairs', 'yue_s2v_epoch',
+           'yue_lgcn_set_graph', 'yue_lgcn_propagate', 'yue_lgcn_grad', 'yue_lgcn_step']
 
 
 class YueHipError(RuntimeError):
@@ -202,6 +203,58 @@ class Device(object):
         j, c = _i32(j)
         loss = C.c_double()
         self._chk(self._lib.yue_adam_step(self._ctx, a, b, c, C.c_int64(len(u)), C.c_double(lr), C.c_double(reg), C.c_int64(step), C.byref(loss)))
+        return loss.value
+
+    def adam_get_moments(self):
+        """(mU, vU, mV, vV) of the uploaded factors' Adam state."""
+        out = [np.empty((r, self.k), np.float32) for r in (self.m, self.m, self.n, self.n)]
+        self._chk(self._lib.yue_adam_get_moments(self._ctx, *[x.ctypes.data_as(C.POINTER(C.c_float)) for x in out]))
+        return tuple(out)
+
+    # -- LightGCN (U = P, V = Q of set_factors; DESIGN.md section 20) -------------------------
+    def lgcn_set_graph(self, m, n, u_ptr, u_items, u_w, i_ptr, i_users, i_w):
+        """Both sides of the (user, item, weight) pair list, ids sorted and unique within a row; checked for symmetry."""
+        u_ptr, a = _i64(u_ptr)
+        i_ptr, d = _i64(i_ptr)
+        assert len(u_ptr) == m + 1 and len(i_ptr) == n + 1, 'lgcn_set_graph: u_ptr [m + 1], i_ptr [n + 1]'
+        assert len(u_items) == len(u_w) and len(i_users) == len(i_w), 'lgcn_set_graph: one weight per id'
+        assert len(u_items) >= u_ptr[-1] and len(i_users) >= i_ptr[-1], 'lgcn_set_graph: ptr runs past the id lists'
+        u_items, b = _i32(u_items if len(u_items) else np.zeros(1, np.int32))
+        u_w, c = _f32(u_w if len(u_w) else np.zeros(1, np.float32))
+        i_users, e = _i32(i_users if len(i_users) else np.zeros(1, np.int32))
+        i_w, f = _f32(i_w if len(i_w) else np.zeros(1, np.float32))
+        self._chk(self._lib.yue_lgcn_set_graph(self._ctx, C.c_int64(m), C.c_int64(n), a, b, c, d, e, f))
+
+    def lgcn_propagate(self, layers, raw=False):
+        """F [m + n][k]; with raw also the unnormalised layers E_1 .. E_layers [layers][m + n][k]."""
+        N = self.m + self.n
+        F = np.empty((N, self.k), np.float32)
+        E = np.empty((max(layers, 0), N, self.k), np.float32) if raw else None
+        self._chk(self._lib.yue_lgcn_propagate(self._ctx, C.c_int(layers), E.ctypes.data_as(C.POINTER(C.c_float)) if raw else None,
+                                               F.ctypes.data_as(C.POINTER(C.c_float))))
+        return (E, F) if raw else F
+
+    def lgcn_grad(self, layers, u, i, j, reg):
+        """(loss, dLoss / dU, dLoss / dV) of one minibatch of triplets; nothing moves."""
+        u, a = _i32(u)
+        i, b = _i32(i)
+        j, c = _i32(j)
+        assert len(u) == len(i) == len(j), 'lgcn_grad: one u, i, j per triplet'
+        loss = C.c_double()
+        gU, gV = np.empty((self.m, self.k), np.float32), np.empty((self.n, self.k), np.float32)
+        self._chk(self._lib.yue_lgcn_grad(self._ctx, C.c_int(layers), a, b, c, C.c_int64(len(u)), C.c_double(reg), C.byref(loss),
+                                          gU.ctypes.data_as(C.POINTER(C.c_float)), gV.ctypes.data_as(C.POINTER(C.c_float))))
+        return loss.value, gU, gV
+
+    def lgcn_step(self, layers, u, i, j, lr, reg, step):
+        """One minibatch step: propagation, loss, backward pass, Adam on U and V.  Returns the loss."""
+        u, a = _i32(u)
+        i, b = _i32(i)
+        j, c = _i32(j)
+        assert len(u) == len(i) == len(j), 'lgcn_step: one u, i, j per triplet'
+        loss = C.c_double()
+        self._chk(self._lib.yue_lgcn_step(self._ctx, C.c_int(layers), a, b, c, C.c_int64(len(u)), C.c_double(lr), C.c_double(reg), C.c_int64(step),
+                                          C.byref(loss)))
         return loss.value
 
     def default_round_events(self):

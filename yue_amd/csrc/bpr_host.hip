@@ -405,6 +405,17 @@ int upload_triplets(yue_ctx *c, const int32_t *u, const int32_t *i, const int32_
     HIPCHK(hipMemcpyAsync(c->xj.p, j, T * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     return YUE_OK;
 }
+// dense Adam on both factor matrices with the gradients in dP / dQ (yue_adam_step, yue_lgcn_step)
+int adam_apply(yue_ctx *c, double lr, int64_t step) {
+    // tf.train.AdamOptimizer defaults; lr_t as _prepare / _apply_sparse_shared form it
+    const double b1 = 0.9, b2 = 0.999;
+    const float lr_t = (float)(lr * std::sqrt(1.0 - std::pow(b2, (double)step)) / (1.0 - std::pow(b1, (double)step)));
+    const int64_t mk = c->m * (int64_t)c->k, nk = c->n * (int64_t)c->k;
+    hipLaunchKernelGGL(yue::k_adam, dim3((unsigned)std::min<int64_t>(8192, (mk + 255) / 256)), dim3(256), 0, c->stream, c->P.p, c->aU_m.p, c->aU_v.p, c->dP.p, mk, lr_t, 0.9f, 0.999f, 1e-8f);
+    hipLaunchKernelGGL(yue::k_adam, dim3((unsigned)std::min<int64_t>(8192, (nk + 255) / 256)), dim3(256), 0, c->stream, c->Q.p, c->aV_m.p, c->aV_v.p, c->dQ.p, nk, lr_t, 0.9f, 0.999f, 1e-8f);
+    HIPCHK(hipGetLastError());
+    return YUE_OK;
+}
 }  // namespace yue_host
 using yue_host::zero_scalars; using yue_host::read_scalars; using yue_host::sumsq_async; using yue_host::upload_triplets;
 
@@ -533,6 +544,19 @@ int yue_adam_reset(yue_ctx *c) {
     return YUE_OK;
 }
 
+int yue_adam_get_moments(yue_ctx *c, float *mU, float *vU, float *mV, float *vV) {
+    if (!c || !c->have_factors || c->adam_m != c->m || c->adam_n != c->n || c->adam_k != c->k)
+        return fail(YUE_ERR_ARG, "yue_adam_get_moments: no Adam state for the uploaded factors");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const size_t mk = (size_t)c->m * c->k * sizeof(float), nk = (size_t)c->n * c->k * sizeof(float);
+    if (mU) HIPCHK(hipMemcpy(mU, c->aU_m.p, mk, hipMemcpyDeviceToHost));
+    if (vU) HIPCHK(hipMemcpy(vU, c->aU_v.p, mk, hipMemcpyDeviceToHost));
+    if (mV) HIPCHK(hipMemcpy(mV, c->aV_m.p, nk, hipMemcpyDeviceToHost));
+    if (vV) HIPCHK(hipMemcpy(vV, c->aV_v.p, nk, hipMemcpyDeviceToHost));
+    return YUE_OK;
+}
+
 int yue_adam_step(yue_ctx *c, const int32_t *u, const int32_t *i, const int32_t *j, int64_t T, double lr, double reg, int64_t step, double *loss_out) {
     if (!c || !c->have_factors) return fail(YUE_ERR_ARG, "yue_adam_step: no factors uploaded");
     if (T <= 0 || !u || !i || !j || step < 1) return fail(YUE_ERR_ARG, "yue_adam_step: bad argument (T > 0, step >= 1)");
@@ -548,13 +572,7 @@ int yue_adam_step(yue_ctx *c, const int32_t *u, const int32_t *i, const int32_t 
     a.reg = (float)reg; a.loss_slots = c->scal.p;
     const dim3 grid((unsigned)(((T + 31) / 32 + 3) / 4));
     with_kr(c->k, [&](auto kr) { hipLaunchKernelGGL(yue::k_mb_grad<kr()>, grid, dim3(256), 0, c->stream, a); });
-    // tf.train.AdamOptimizer defaults; lr_t as _prepare / _apply_sparse_shared form it
-    const double b1 = 0.9, b2 = 0.999;
-    const float lr_t = (float)(lr * std::sqrt(1.0 - std::pow(b2, (double)step)) / (1.0 - std::pow(b1, (double)step)));
-    const int64_t mk = c->m * (int64_t)c->k, nk = c->n * (int64_t)c->k;
-    hipLaunchKernelGGL(yue::k_adam, dim3((unsigned)std::min<int64_t>(8192, (mk + 255) / 256)), dim3(256), 0, c->stream, c->P.p, c->aU_m.p, c->aU_v.p, c->dP.p, mk, lr_t, 0.9f, 0.999f, 1e-8f);
-    hipLaunchKernelGGL(yue::k_adam, dim3((unsigned)std::min<int64_t>(8192, (nk + 255) / 256)), dim3(256), 0, c->stream, c->Q.p, c->aV_m.p, c->aV_v.p, c->dQ.p, nk, lr_t, 0.9f, 0.999f, 1e-8f);
-    HIPCHK(hipGetLastError());
+    if ((rc = yue_host::adam_apply(c, lr, step))) return rc;
     return read_scalars(c, loss_out, nullptr, nullptr);
 }
 

@@ -9,6 +9,7 @@
 //   cof_host.hip    CoFactor (co-occurrence, level-scheduled item sweep)
 //   cnet_host.hip   CUNE's user-network stage (walks, embedding, friends); Song2vec's track embedding (sentences)
 //   s2v_host.hip    Song2vec's iteration (level-scheduled rating steps and similarity pairs)
+//   lgcn_host.hip   LightGCN (graph propagation forward and backward, minibatch, Adam step)
 #pragma once
 #include "../../include/yue_hip.h"
 
@@ -30,6 +31,7 @@ struct yue_expo;                                     // expo_host.hip: mu, Gram 
 struct yue_cof;                                      // cof_host.hip: co-occurrence CSR, SPPMI, level schedule, G / w / c of CoFactor
 struct yue_cnet;                                     // cnet_host.hip: pairs, walks, embedding, friends of CUNE's user-network stage
 struct yue_s2v;                                      // s2v_host.hip: biases, steps, pairs and their level schedules of Song2vec's iteration
+struct yue_lgcn;                                     // lgcn_host.hip: graph CSR, hub parts, layers and gradients of LightGCN
 struct yue_ipf;                                      // ipf_host.hip: session temporal graph, weights, per-slot work arrays of IPF
 
 namespace yue_host {
@@ -215,6 +217,10 @@ struct yue_ctx {
     yue_cof *cof = nullptr;              // CoFactor state (yue_cof_*), owned by cof_host.hip
     yue_cnet *cnet = nullptr;            // CUNE user-network state (yue_cnet_*), owned by cnet_host.hip
     yue_s2v *s2v = nullptr;              // Song2vec state (yue_s2v_*), owned by s2v_host.hip
+    yue_lgcn *lgcn = nullptr;            // LightGCN state (yue_lgcn_*), owned by lgcn_host.hip
+    int64_t opt_lgcn_hub = 1024;         // LightGCN: rows with more neighbours are cut into parts of this many, one wave each (lgcn_kernels.hpp)
+    int64_t lgcn_hubs = 0, lgcn_parts = 0;   // ... such rows and their parts in the last call (read-only options lgcn_last_hubs / lgcn_last_parts)
+    int64_t lgcn_ns[4] = {0, 0, 0, 0};   // device time of the last call's forward, minibatch, backward and Adam phases (read-only options lgcn_last_*_ns)
 };
 
 namespace yue_host {
@@ -226,6 +232,7 @@ int zero_scalars(yue_ctx *c);
 int read_scalars(yue_ctx *c, double *nll, double *sp, double *sq);
 int sumsq_async(yue_ctx *c, const double *p_slots = nullptr);   // p_slots: sum P*P from these kNllSlots partial sums instead of a pass over P
 int upload_triplets(yue_ctx *c, const int32_t *u, const int32_t *i, const int32_t *j, int64_t T, bool validate);
+int adam_apply(yue_ctx *c, double lr, int64_t step);            // k_adam on P and Q with the gradients in dP / dQ, lr_t of `step`
 // comm.hip: sum dP[first .. first + count) over the ranks on `stream` (in place); identity without a communicator
 int reduce_user_block(yue_ctx *c, int64_t first, int64_t count, hipStream_t stream);
 // chain_host.hip: exact sequential semantics over the uploaded events (negatives in ev_j) / over the stream in xu, xi, xj
@@ -271,4 +278,6 @@ int cnet_get_option(yue_ctx *c, const std::string &key, int64_t *value);
 void s2v_release(yue_ctx *c);
 int s2v_set_option(yue_ctx *c, const std::string &key, int64_t value);
 int s2v_get_option(yue_ctx *c, const std::string &key, int64_t *value);
+// lgcn_host.hip: frees the LightGCN state (its options are rows of the option table)
+void lgcn_release(yue_ctx *c);
 }  // namespace yue_host

@@ -116,6 +116,14 @@ const Option kOptions[] = {
     {"chain_last_runs", YUE_AT(chain_runs)},          // last exact launch: runs walked, waves launched
     {"chain_last_waves", YUE_AT(chain_waves)},
     {"replay_last_levels", YUE_AT(replay_levels)},    // last levelled replay: dependency levels = launches
+    // LightGCN (lgcn_host.hip)
+    {"lgcn_hub", YUE_AT(opt_lgcn_hub), set_ranged, 1, 0x7fffffff, "must be 1 .. 2^31 - 1"},
+    {"lgcn_last_hubs", YUE_AT(lgcn_hubs)},
+    {"lgcn_last_parts", YUE_AT(lgcn_parts)},
+    {"lgcn_last_forward_ns", YUE_AT(lgcn_ns[0])},
+    {"lgcn_last_batch_ns", YUE_AT(lgcn_ns[1])},
+    {"lgcn_last_backward_ns", YUE_AT(lgcn_ns[2])},
+    {"lgcn_last_adam_ns", YUE_AT(lgcn_ns[3])},
 };
 #undef YUE_AT
 
