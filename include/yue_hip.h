@@ -411,7 +411,7 @@ int yue_ipf_topn(yue_ctx *ctx, const int32_t *users, int64_t nu, int N, int32_t 
 /*
  * CUNE's user-network stage (reference recommender/advanced/CUNE.py:34-118) -- collaborative user network, random walks,
  * CBOW user embedding, cosine top-K friends.  Needs no factors.  Contract: tests/helpers/numpy_cune_net.py, DESIGN.md 18.
- * Every random number is cnet_hash(seed ^ tag, a, b, c, d) (csrc/cnet_kernels.hpp: the mix64 chain of the BPR sampler).
+ * Every random number is cnet_hash(seed ^ tag, a, b, c, d) (csrc/counter_hash.hpp: the mix64 chain of the BPR sampler).
  *   yue_cnet_set_pairs     the distinct (user, item) pairs both ways, as yue_knn_set_pairs takes them (no counts).  The
  *                        network CUNet[a] = every other user b repeated |items(a) & items(b)| times is never built: entry
  *                        r of it is found from the prefix sums of deg(item) - 1 over a's item row.  A user whose total is 0
@@ -514,6 +514,39 @@ int yue_lgcn_grad(yue_ctx *ctx, int layers, const int32_t *u, const int32_t *i, 
                   float *gU_out, float *gV_out);
 int yue_lgcn_step(yue_ctx *ctx, int layers, const int32_t *u, const int32_t *i, const int32_t *j, int64_t T, double lr, double reg, int64_t step,
                   double *loss_out);
+
+/* NGCF (reference recommender/advanced/NGCF.py).  U [m][k] and V [n][k] are the factors of
+ * yue_set_factors; the Adam moments of U and V are those of yue_adam_step (yue_adam_reset clears them).  With N = m + n:
+ *   A  [N][N], a general CSR (the reference's graph is not symmetric as written); the transpose is built on the host.
+ *   Per layer l = 0 .. layers-1, E_0 = [U; V]:  S = A E;  Z = (S + E) W_l_1 + (E o S) W_l_2;  H = Z > 0 ? Z : 0.2 Z;
+ *   D = training ? H / keep where the mask keeps the element, 0 elsewhere : H;  E_{l+1} = D;  N_{l+1} = D * rsqrt(max(|D row|^2, 1e-12)).
+ *   F = [E_0 | N_1 | .. | N_layers], (layers + 1) k wide.  The loss is yue_lgcn_grad's on F.
+ *   The mask keeps element (row, column) of layer l when the top 24 bits of hash(seed ^ 0x4E474346, step, l, row, column) lie
+ *   below floor(keep * 2^24); the hash is the user-network stage's counter hash.  It is recomputed in the backward pass.
+ *   yue_ngcf_set_graph    ptr [N + 1], col, w: columns ascending and unique within a row and below N, finite weights; checked
+ *                         before anything is stored (a refused call leaves the previous graph in place).
+ *   yue_ngcf_set_weights  W [layers][2][k][k] (W_l_1 then W_l_2, input index major); clears the weights' Adam moments.
+ *   yue_ngcf_get_weights  W and, where asked for, the weights' moments (any pointer may be NULL).
+ *   yue_ngcf_propagate    S_out, Z_out, D_out [layers][N][k], F_out [N][(layers + 1) k] (any may be NULL).
+ *   yue_ngcf_grad         loss, dLoss / dU [m][k], dLoss / dV [n][k], dLoss / dW [layers][2][k][k]; no step (outputs may be NULL).
+ *   yue_ngcf_step         the same, then dense Adam (beta 0.9 / 0.999, eps 1e-8, lr_t of `step` = 1, 2, ...) on U, V and the
+ *                         weights; the mask is that of `step`.
+ * Refused with YUE_ERR_ARG: k > 128, (layers + 1) k > 256, layers < 1, keep outside (0, 1], T < 1, an id out of range, no graph or
+ * no weights, a graph or weights set for other shapes.
+ * Every sum has a fixed order and no atomic is used: two calls on the same input return the same bits.  The weight gradients
+ * are summed over chunks of 512 rows in ascending order.  Option "ngcf_hub" (default 1024) as "lgcn_hub", for A and its
+ * transpose.  Read-only options "ngcf_last_hubs", "ngcf_last_parts" (both matrices together), "ngcf_last_gather_ns",
+ * "ngcf_last_dense_ns", "ngcf_last_batch_ns", "ngcf_last_backward_ns", "ngcf_last_wgrad_ns", "ngcf_last_adam_ns".
+ */
+int yue_ngcf_set_graph(yue_ctx *ctx, int64_t m, int64_t n, const int64_t *ptr, const int32_t *col, const float *w);
+int yue_ngcf_set_weights(yue_ctx *ctx, int layers, int k, const float *W);
+int yue_ngcf_get_weights(yue_ctx *ctx, float *W, float *mW, float *vW);
+int yue_ngcf_propagate(yue_ctx *ctx, int layers, int training, double keep, uint64_t seed, int64_t step, float *S_out, float *Z_out, float *D_out,
+                       float *F_out);
+int yue_ngcf_grad(yue_ctx *ctx, int layers, int training, double keep, uint64_t seed, int64_t step, const int32_t *u, const int32_t *i,
+                  const int32_t *j, int64_t T, double reg, double *loss_out, float *gU_out, float *gV_out, float *gW_out);
+int yue_ngcf_step(yue_ctx *ctx, int layers, int training, double keep, uint64_t seed, const int32_t *u, const int32_t *i, const int32_t *j,
+                  int64_t T, double lr, double reg, int64_t step, double *loss_out);
 
 /* Multi-GPU (one process per GPU, RCCL over xGMI).  Rank 0 creates the id, the caller ships
  * the 128 bytes to the other ranks (any side channel), every rank calls yue_comm_init. */

@@ -33,7 +33,8 @@ SYMBOLS = ['yue_last_error', 'yue_version', 'yue_ctx_create', 'yue_ctx_destroy',
            'yue_cnet_set_pairs', 'yue_cnet_walks', 'yue_cnet_set_walks', 'yue_cnet_set_sentences', 'yue_cnet_embed', 'yue_cnet_set_embedding',
            'yue_cnet_friends',
            'yue_s2v_set_state', 'yue_s2v_get_state', 'yue_s2v_set_steps', 'yue_s2v_set_pairs', 'yue_s2v_epoch',
-           'yue_lgcn_set_graph', 'yue_lgcn_propagate', 'yue_lgcn_grad', 'yue_lgcn_step']
+           'yue_lgcn_set_graph', 'yue_lgcn_propagate', 'yue_lgcn_grad', 'yue_lgcn_step',
+           'yue_ngcf_set_graph', 'yue_ngcf_set_weights', 'yue_ngcf_get_weights', 'yue_ngcf_propagate', 'yue_ngcf_grad', 'yue_ngcf_step']
 
 
 class YueHipError(RuntimeError):
@@ -255,6 +256,64 @@ class Device(object):
         loss = C.c_double()
         self._chk(self._lib.yue_lgcn_step(self._ctx, C.c_int(layers), a, b, c, C.c_int64(len(u)), C.c_double(lr), C.c_double(reg), C.c_int64(step),
                                           C.byref(loss)))
+        return loss.value
+
+    # -- NGCF (U = P, V = Q of set_factors) ------------------------------
+    def ngcf_set_graph(self, m, n, ptr, col, w):
+        """The (m + n)-row graph as a general CSR: columns ascending and unique within a row."""
+        ptr, a = _i64(ptr)
+        assert len(ptr) == m + n + 1 and len(col) == len(w) and len(col) >= ptr[-1], 'ngcf_set_graph: ptr [m + n + 1], one weight per column'
+        col, b = _i32(col if len(col) else np.zeros(1, np.int32))
+        w, c = _f32(w if len(w) else np.zeros(1, np.float32))
+        self._chk(self._lib.yue_ngcf_set_graph(self._ctx, C.c_int64(m), C.c_int64(n), a, b, c))
+
+    def ngcf_set_weights(self, W):
+        """W [layers][2][k][k]; the weights' Adam moments are cleared."""
+        W, a = _f32(W)
+        assert W.ndim == 4 and W.shape[1] == 2 and W.shape[2] == W.shape[3], 'ngcf_set_weights: W [layers][2][k][k]'
+        self.ngcf_w_shape = W.shape
+        self._chk(self._lib.yue_ngcf_set_weights(self._ctx, C.c_int(W.shape[0]), C.c_int(W.shape[2]), a))
+
+    def ngcf_get_weights(self, moments=False):
+        """W, or (W, mW, vW) with the weights' Adam moments."""
+        out = [np.empty(self.ngcf_w_shape, np.float32) for _ in range(3 if moments else 1)]
+        ptrs = [x.ctypes.data_as(C.POINTER(C.c_float)) for x in out] + [None] * (3 - len(out))
+        self._chk(self._lib.yue_ngcf_get_weights(self._ctx, *ptrs))
+        return tuple(out) if moments else out[0]
+
+    def ngcf_propagate(self, layers, training=False, keep=1.0, seed=0, step=0, parts=False):
+        """F [m + n][(layers + 1) k]; with parts (S, Z, D, F), the first three [layers][m + n][k]."""
+        N = self.m + self.n
+        F = np.empty((N, (max(layers, 0) + 1) * self.k), np.float32)
+        P = [np.empty((max(layers, 0), N, self.k), np.float32) for _ in range(3)] if parts else []
+        ptrs = [x.ctypes.data_as(C.POINTER(C.c_float)) for x in P] if parts else [None] * 3
+        self._chk(self._lib.yue_ngcf_propagate(self._ctx, C.c_int(layers), C.c_int(int(bool(training))), C.c_double(keep), C.c_uint64(seed),
+                                               C.c_int64(step), ptrs[0], ptrs[1], ptrs[2], F.ctypes.data_as(C.POINTER(C.c_float))))
+        return tuple(P) + (F,) if parts else F
+
+    def ngcf_grad(self, layers, training, keep, seed, step, u, i, j, reg):
+        """(loss, dLoss / dU, dLoss / dV, dLoss / dW) of one minibatch of triplets; nothing moves."""
+        u, a = _i32(u)
+        i, b = _i32(i)
+        j, c = _i32(j)
+        assert len(u) == len(i) == len(j), 'ngcf_grad: one u, i, j per triplet'
+        loss = C.c_double()
+        gU, gV = np.empty((self.m, self.k), np.float32), np.empty((self.n, self.k), np.float32)
+        gW = np.empty((max(layers, 0), 2, self.k, self.k), np.float32)
+        self._chk(self._lib.yue_ngcf_grad(self._ctx, C.c_int(layers), C.c_int(int(bool(training))), C.c_double(keep), C.c_uint64(seed), C.c_int64(step),
+                                          a, b, c, C.c_int64(len(u)), C.c_double(reg), C.byref(loss), gU.ctypes.data_as(C.POINTER(C.c_float)),
+                                          gV.ctypes.data_as(C.POINTER(C.c_float)), gW.ctypes.data_as(C.POINTER(C.c_float))))
+        return loss.value, gU, gV, gW
+
+    def ngcf_step(self, layers, training, keep, seed, u, i, j, lr, reg, step):
+        """One minibatch step: propagation, loss, backward pass, Adam on U, V and the weights.  Returns the loss."""
+        u, a = _i32(u)
+        i, b = _i32(i)
+        j, c = _i32(j)
+        assert len(u) == len(i) == len(j), 'ngcf_step: one u, i, j per triplet'
+        loss = C.c_double()
+        self._chk(self._lib.yue_ngcf_step(self._ctx, C.c_int(layers), C.c_int(int(bool(training))), C.c_double(keep), C.c_uint64(seed), a, b, c,
+                                          C.c_int64(len(u)), C.c_double(lr), C.c_double(reg), C.c_int64(step), C.byref(loss)))
         return loss.value
 
     def default_round_events(self):

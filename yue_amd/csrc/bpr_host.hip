@@ -405,16 +405,19 @@ int upload_triplets(yue_ctx *c, const int32_t *u, const int32_t *i, const int32_
     HIPCHK(hipMemcpyAsync(c->xj.p, j, T * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     return YUE_OK;
 }
-// dense Adam on both factor matrices with the gradients in dP / dQ (yue_adam_step, yue_lgcn_step)
-int adam_apply(yue_ctx *c, double lr, int64_t step) {
-    // tf.train.AdamOptimizer defaults; lr_t as _prepare / _apply_sparse_shared form it
+// dense Adam on one parameter with moments and gradient of its own: tf.train.AdamOptimizer defaults; lr_t as _prepare /
+// _apply_sparse_shared form it
+int adam_apply_dense(yue_ctx *c, float *var, float *m, float *v, float *grad, int64_t count, double lr, int64_t step) {
     const double b1 = 0.9, b2 = 0.999;
     const float lr_t = (float)(lr * std::sqrt(1.0 - std::pow(b2, (double)step)) / (1.0 - std::pow(b1, (double)step)));
-    const int64_t mk = c->m * (int64_t)c->k, nk = c->n * (int64_t)c->k;
-    hipLaunchKernelGGL(yue::k_adam, dim3((unsigned)std::min<int64_t>(8192, (mk + 255) / 256)), dim3(256), 0, c->stream, c->P.p, c->aU_m.p, c->aU_v.p, c->dP.p, mk, lr_t, 0.9f, 0.999f, 1e-8f);
-    hipLaunchKernelGGL(yue::k_adam, dim3((unsigned)std::min<int64_t>(8192, (nk + 255) / 256)), dim3(256), 0, c->stream, c->Q.p, c->aV_m.p, c->aV_v.p, c->dQ.p, nk, lr_t, 0.9f, 0.999f, 1e-8f);
+    hipLaunchKernelGGL(yue::k_adam, dim3((unsigned)std::min<int64_t>(8192, (count + 255) / 256)), dim3(256), 0, c->stream, var, m, v, grad, count, lr_t, 0.9f, 0.999f, 1e-8f);
     HIPCHK(hipGetLastError());
     return YUE_OK;
+}
+// ... on both factor matrices with the gradients in dP / dQ (yue_adam_step, yue_lgcn_step, yue_ngcf_step)
+int adam_apply(yue_ctx *c, double lr, int64_t step) {
+    const int rc = adam_apply_dense(c, c->P.p, c->aU_m.p, c->aU_v.p, c->dP.p, c->m * (int64_t)c->k, lr, step);
+    return rc ? rc : adam_apply_dense(c, c->Q.p, c->aV_m.p, c->aV_v.p, c->dQ.p, c->n * (int64_t)c->k, lr, step);
 }
 }  // namespace yue_host
 using yue_host::zero_scalars; using yue_host::read_scalars; using yue_host::sumsq_async; using yue_host::upload_triplets;

@@ -16,6 +16,7 @@
 //              (cosine descending, id ascending); no m x m array.
 #pragma once
 #include "bpr_device.hpp"
+#include "counter_hash.hpp"
 
 #include <climits>
 
@@ -34,18 +35,6 @@ constexpr float kCnetMaxExp = 6.0f;
 // stream tags (xor-ed into the seed): one independent stream per use
 constexpr uint64_t kCnetTagWalk = 0, kCnetTagShuffle = 0x5348554646ull, kCnetTagInit = 0x494E4954ull, kCnetTagSub = 0x535542ull,
                    kCnetTagWin = 0x57494Eull, kCnetTagNeg = 0x4E4547ull;
-
-// 64 uniform bits for the counter (a, b, c, d) of stream `seed`: bpr_device.hpp's mix64, chained as ctr_draw chains it
-__host__ __device__ inline uint64_t cnet_mix(uint64_t z) {
-    z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-    z ^= z >> 27; z *= 0x94D049BB133111EBull;
-    z ^= z >> 31; return z;
-}
-__host__ __device__ inline uint64_t cnet_hash(uint64_t seed, uint64_t a, uint64_t b, uint64_t c, uint64_t d) {
-    uint64_t z = cnet_mix(seed + 0x9E3779B97F4A7C15ull * (a + 1));
-    z = cnet_mix(z ^ (0xD1B54A32D192ED03ull * (b + 1) + 0x8CB92BA72F3D8DD7ull * c));
-    return cnet_mix(z ^ (0xA0761D6478BD642Full * (d + 1)));
-}
 
 struct CnetArgs {
     int64_t m, n;

@@ -10,6 +10,7 @@
 //   cnet_host.hip   CUNE's user-network stage (walks, embedding, friends); Song2vec's track embedding (sentences)
 //   s2v_host.hip    Song2vec's iteration (level-scheduled rating steps and similarity pairs)
 //   lgcn_host.hip   LightGCN (graph propagation forward and backward, minibatch, Adam step)
+//   ngcf_host.hip   NGCF (weighted graph convolution: gather, MFMA layers forward and backward, weight gradients, Adam step)
 #pragma once
 #include "../../include/yue_hip.h"
 
@@ -32,6 +33,7 @@ struct yue_cof;                                      // cof_host.hip: co-occurre
 struct yue_cnet;                                     // cnet_host.hip: pairs, walks, embedding, friends of CUNE's user-network stage
 struct yue_s2v;                                      // s2v_host.hip: biases, steps, pairs and their level schedules of Song2vec's iteration
 struct yue_lgcn;                                     // lgcn_host.hip: graph CSR, hub parts, layers and gradients of LightGCN
+struct yue_ngcf;                                     // ngcf_host.hip: graph CSR and its transpose, weights, layers and gradients of NGCF
 struct yue_ipf;                                      // ipf_host.hip: session temporal graph, weights, per-slot work arrays of IPF
 
 namespace yue_host {
@@ -221,6 +223,10 @@ struct yue_ctx {
     int64_t opt_lgcn_hub = 1024;         // LightGCN: rows with more neighbours are cut into parts of this many, one wave each (lgcn_kernels.hpp)
     int64_t lgcn_hubs = 0, lgcn_parts = 0;   // ... such rows and their parts in the last call (read-only options lgcn_last_hubs / lgcn_last_parts)
     int64_t lgcn_ns[4] = {0, 0, 0, 0};   // device time of the last call's forward, minibatch, backward and Adam phases (read-only options lgcn_last_*_ns)
+    yue_ngcf *ngcf = nullptr;            // NGCF state (yue_ngcf_*), owned by ngcf_host.hip
+    int64_t opt_ngcf_hub = 1024;         // NGCF: as lgcn_hub, for the graph and its transpose
+    int64_t ngcf_hubs = 0, ngcf_parts = 0;   // ... hub rows and parts of both matrices in the last call (read-only options ngcf_last_hubs / ngcf_last_parts)
+    int64_t ngcf_ns[6] = {0, 0, 0, 0, 0, 0};   // device time of the last call's gather, dense, batch, backward, wgrad and adam phases (read-only options ngcf_last_*_ns)
 };
 
 namespace yue_host {
@@ -233,6 +239,8 @@ int read_scalars(yue_ctx *c, double *nll, double *sp, double *sq);
 int sumsq_async(yue_ctx *c, const double *p_slots = nullptr);   // p_slots: sum P*P from these kNllSlots partial sums instead of a pass over P
 int upload_triplets(yue_ctx *c, const int32_t *u, const int32_t *i, const int32_t *j, int64_t T, bool validate);
 int adam_apply(yue_ctx *c, double lr, int64_t step);            // k_adam on P and Q with the gradients in dP / dQ, lr_t of `step`
+// ... the same step on any dense parameter with moments and gradient of its own (NGCF's weights)
+int adam_apply_dense(yue_ctx *c, float *var, float *m, float *v, float *grad, int64_t count, double lr, int64_t step);
 // comm.hip: sum dP[first .. first + count) over the ranks on `stream` (in place); identity without a communicator
 int reduce_user_block(yue_ctx *c, int64_t first, int64_t count, hipStream_t stream);
 // chain_host.hip: exact sequential semantics over the uploaded events (negatives in ev_j) / over the stream in xu, xi, xj
@@ -280,4 +288,6 @@ int s2v_set_option(yue_ctx *c, const std::string &key, int64_t value);
 int s2v_get_option(yue_ctx *c, const std::string &key, int64_t *value);
 // lgcn_host.hip: frees the LightGCN state (its options are rows of the option table)
 void lgcn_release(yue_ctx *c);
+// ngcf_host.hip: frees the NGCF state (its options are rows of the option table)
+void ngcf_release(yue_ctx *c);
 }  // namespace yue_host

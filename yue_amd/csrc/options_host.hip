@@ -124,6 +124,16 @@ const Option kOptions[] = {
     {"lgcn_last_batch_ns", YUE_AT(lgcn_ns[1])},
     {"lgcn_last_backward_ns", YUE_AT(lgcn_ns[2])},
     {"lgcn_last_adam_ns", YUE_AT(lgcn_ns[3])},
+    // NGCF (ngcf_host.hip)
+    {"ngcf_hub", YUE_AT(opt_ngcf_hub), set_ranged, 1, 0x7fffffff, "must be 1 .. 2^31 - 1"},
+    {"ngcf_last_hubs", YUE_AT(ngcf_hubs)},
+    {"ngcf_last_parts", YUE_AT(ngcf_parts)},
+    {"ngcf_last_gather_ns", YUE_AT(ngcf_ns[0])},
+    {"ngcf_last_dense_ns", YUE_AT(ngcf_ns[1])},
+    {"ngcf_last_batch_ns", YUE_AT(ngcf_ns[2])},
+    {"ngcf_last_backward_ns", YUE_AT(ngcf_ns[3])},
+    {"ngcf_last_wgrad_ns", YUE_AT(ngcf_ns[4])},
+    {"ngcf_last_adam_ns", YUE_AT(ngcf_ns[5])},
 };
 #undef YUE_AT
 
