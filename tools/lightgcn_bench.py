@@ -9,7 +9,7 @@ Weights are the squared event counts, as the reference's graph has them.  One JS
 Algorithmic bytes of one product: every entry gathers a k-float row and reads its (index, weight) = nnz (4 k + 8); every row
 reads its two pointers' share and writes k floats (forward: also reads and writes the running sum F) = N (4 k [+ 8 k] + 8).
 
-    python tools/lightgcn_bench.py [--graphs c2,c3] [--steps 5] [--batch 2048] [--hub 1024]
+    python tools/lightgcn_bench.py [--graphs c2,c3] [--steps 5] [--batch 2048] [--hub 1024]      (YUE_LIB=path of another build of the library)
 """
 import argparse
 import json
@@ -22,8 +22,11 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from yue_amd import _shim                      # noqa: E402
 from yue_amd import synth                      # noqa: E402
 from yue_amd._shim import Device               # noqa: E402
+if os.environ.get('YUE_LIB'):
+    _shim.LIB_PATH = os.environ['YUE_LIB']
 
 GRAPHS = {'c2': (100000, 50000, 50, 64), 'c3': (1000000, 200000, 50, 128), 'tiny': (2000, 500, 20, 64)}
 PEAK = 8e12

@@ -11,7 +11,7 @@ One JSON line per graph.
 Algorithmic bytes of one forward product: every entry gathers a k-float row and reads its (index, weight) = nnz (4 k + 8);
 every row reads its two pointers' share and writes k floats = N (4 k + 8).
 
-    python tools/ngcf_bench.py [--graphs c2,c3] [--steps 5] [--batch 2048] [--hub 1024]
+    python tools/ngcf_bench.py [--graphs c2,c3] [--steps 5] [--batch 2048] [--hub 1024]      (YUE_LIB=path of another build of the library)
 """
 import argparse
 import json
@@ -24,8 +24,11 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from yue_amd import _shim                      # noqa: E402
 from yue_amd import synth                      # noqa: E402
 from yue_amd._shim import Device               # noqa: E402
+if os.environ.get('YUE_LIB'):
+    _shim.LIB_PATH = os.environ['YUE_LIB']
 
 GRAPHS = {'c2': (100000, 50000, 50), 'c3': (1000000, 200000, 50), 'tiny': (2000, 500, 20)}
 K, LAYERS, PEAK = 64, 3, 8e12

@@ -11,6 +11,8 @@
 //   s2v_host.hip    Song2vec's iteration (level-scheduled rating steps and similarity pairs)
 //   lgcn_host.hip   LightGCN (graph propagation forward and backward, minibatch, Adam step)
 //   ngcf_host.hip   NGCF (weighted graph convolution: gather, MFMA layers forward and backward, weight gradients, Adam step)
+//   gcn_host.hpp    what those two share (header only): the graph on the device and its hub parts, a product's launches, the
+//                   minibatch, the phase timer
 #pragma once
 #include "../../include/yue_hip.h"
 
@@ -32,8 +34,8 @@ struct yue_expo;                                     // expo_host.hip: mu, Gram 
 struct yue_cof;                                      // cof_host.hip: co-occurrence CSR, SPPMI, level schedule, G / w / c of CoFactor
 struct yue_cnet;                                     // cnet_host.hip: pairs, walks, embedding, friends of CUNE's user-network stage
 struct yue_s2v;                                      // s2v_host.hip: biases, steps, pairs and their level schedules of Song2vec's iteration
-struct yue_lgcn;                                     // lgcn_host.hip: graph CSR, hub parts, layers and gradients of LightGCN
-struct yue_ngcf;                                     // ngcf_host.hip: graph CSR and its transpose, weights, layers and gradients of NGCF
+struct yue_lgcn;                                     // lgcn_host.hip: the graph (gcn_host.hpp), layers and gradients of LightGCN
+struct yue_ngcf;                                     // ngcf_host.hip: the graph and its transpose (gcn_host.hpp), weights, layers and gradients of NGCF
 struct yue_ipf;                                      // ipf_host.hip: session temporal graph, weights, per-slot work arrays of IPF
 
 namespace yue_host {

@@ -1,7 +1,8 @@
 // LightGCN kernels for gfx950 (reference recommender/advanced/LightGCN.py): the sparse-times-dense
 // propagation over the (m + n)-row user-item graph with its fused epilogues, forward and backward, and the minibatch's
-// loss / dF.  Everything float32 as TensorFlow computes it; loss partials in double.  No atomics: every output row has one
-// writer and every sum a fixed order, so two runs on the same input give the same bits.
+// loss / dF.  NGCF (ngcf_kernels.hpp) runs its products and its minibatch through the same kernels; the
+// host side of both is gcn_host.hpp.  Everything float32 as TensorFlow computes it; loss partials in double.  No atomics:
+// every output row has one writer and every sum a fixed order, so two runs on the same input give the same bits.
 //
 // Wave layout as in train_kernels.hpp: lane l holds elements 64*r + l (r < KR) of a row, k <= 128.
 //   k_lgcn_rows   a wave takes `rpw` consecutive rows (many where the mean degree is small); per row it loads 64
@@ -14,7 +15,9 @@
 //   kFwd   Y[row] = acc; ss[row] = sum acc^2; F[row] += acc * (1 / sqrt(max(ss, 1e-12)))              (LightGCN.py:40-45)
 //   kBwd   out[row] = J(G[row]) + acc, J(g) = (g - nh (nh . g)) * rinv with nh = E[row] * rinv where ss >= 1e-12, g * 1e6 elsewhere
 //          (the derivative of x * rsqrt(max(sum x^2, 1e-12))); `gather` = 0 for the last layer, which has no A . gE term
-//   kFin   g[U;V][row] = G[row] + acc, user rows to gU, item rows to gV
+//   kPlain out[row] = (base ? base[row] : 0) + acc, rows below m to outU, the others to outV (out may be base).  LightGCN's
+//          last backward product: base = G into the two gradient buffers; NGCF's S = A E (no base), its A^T gS added onto the
+//          local part in place, and its last one into the two gradient buffers
 #pragma once
 #include "bpr_device.hpp"
 
@@ -23,10 +26,10 @@ namespace yue {
 constexpr int kLgcnMaxK = 128;
 constexpr float kLgcnEps = 1e-12f;                   // tf.nn.l2_normalize's epsilon
 
-enum { kLgcnFwd = 0, kLgcnBwd = 1, kLgcnFin = 2 };
+enum { kLgcnFwd = 0, kLgcnBwd = 1, kLgcnPlain = 2 };
 
 struct LgcnArgs {
-    const int64_t *ptr;                              // [N + 1] CSR of the symmetric graph, N = m + n
+    const int64_t *ptr;                              // [N + 1] CSR of the graph (LightGCN: symmetric), N = m + n
     const int32_t *col;
     const float *w;
     const float *X;                                  // [N, k] the gathered matrix (E_{l-1} forward, gE_{l+1} backward)
@@ -35,8 +38,10 @@ struct LgcnArgs {
     int64_t hub;                                     // rows with more neighbours than this are the hub kernels'
     // epilogue
     float *Y, *ss, *F;                               // kFwd: raw layer, its row sums of squares, the running sum of layers
-    const float *G, *E, *ssr;                        // kBwd / kFin: dLoss / dF; kBwd: the raw layer and its sums of squares
-    float *out, *gU, *gV;                            // kBwd: gE_l; kFin: the two gradients
+    const float *G, *E, *ssr;                        // kBwd: dLoss / dF, the raw layer and its sums of squares
+    float *out;                                      // kBwd: gE_l
+    const float *base;                               // kPlain: [N, k] added to the product, or null
+    float *outU, *outV;                              // kPlain: rows below m, the other rows (each from its first row)
     // hubs
     const int64_t *hub_row, *hub_part_ptr;           // [H] rows, [H + 1] first part of every hub
     const int64_t *part_beg, *part_end;              // [parts] neighbour ranges
@@ -146,11 +151,11 @@ __device__ __forceinline__ void lgcn_epilogue(const LgcnArgs &a, int64_t row, in
             if (el < k) a.out[row * k + el] = j[r] + acc[r];
         }
     } else {
-        float *dst = row < a.m ? a.gU + row * k : a.gV + (row - a.m) * k;
+        float *dst = row < a.m ? a.outU + row * k : a.outV + (row - a.m) * k;
 #pragma unroll
         for (int r = 0; r < KR; ++r) {
             const int el = 64 * r + lane;
-            if (el < k) dst[el] = a.G[row * k + el] + acc[r];
+            if (el < k) dst[el] = (a.base ? a.base[row * k + el] : 0.0f) + acc[r];
         }
     }
 }

@@ -1,61 +1,34 @@
 // libyue_hip.so -- NGCF (reference recommender/advanced/NGCF.py): the weighted user-item graph and its transpose, the layers
 // forward and backward with their two k x k weights, the minibatch and the Adam step (include/yue_hip.h).
-// Kernels: ngcf_kernels.hpp on top of lgcn_kernels.hpp (gather, hub parts, minibatch); Adam is k_adam through
-// yue_host::adam_apply (U, V: the context's P, Q and moments) and yue_host::adam_apply_dense (the weights, moments kept here).
-#include "host_common.hpp"
+// Kernels: ngcf_kernels.hpp (the dense half of a layer, the weight gradients) and lgcn_kernels.hpp (products, minibatch); the
+// graphs on the device, a product's launches, the minibatch and the phase timer are gcn_host.hpp's, shared with lgcn_host.hip;
+// Adam is k_adam through yue_host::adam_apply (U, V: the context's P, Q and moments) and yue_host::adam_apply_dense (the
+// weights, moments kept here).
+#include "gcn_host.hpp"
 
 #include "ngcf_kernels.hpp"
 
-#include <utility>
-
+using gcn::upload;
 using yue_host::fail;
-using yue_host::with_kr;
-
-namespace {
-
-// one sparse matrix: CSR on host (row pointers) and device, and the hub rows' parts for the threshold they were built with
-struct Csr {
-    std::vector<int64_t> h_ptr;
-    DevBuf<int64_t> ptr;
-    DevBuf<int32_t> col;
-    DevBuf<float> w;
-    int rpw = 1;
-    int64_t hub_built = -1, H = 0, parts = 0;
-    DevBuf<int64_t> hub_row, hub_part_ptr, part_beg, part_end;
-    void release() {
-        ptr.release(); col.release(); w.release(); hub_row.release(); hub_part_ptr.release(); part_beg.release(); part_end.release();
-    }
-};
-
-enum { kGather = 0, kDense = 1, kBatch = 2, kBackward = 3, kWgrad = 4, kAdam = 5, kPhases = 6 };
-
-}  // namespace
 
 struct yue_ngcf {
     int64_t m = 0, n = 0, nnz = 0;
     bool have_graph = false;
-    Csr A, At;
-    DevBuf<float> partial;                           // hub parts of the running product
+    gcn::Graph A, At;                                // their hub rows follow the option ngcf_hub
+    DevBuf<float> partial;                           // hub parts of the running product, sized for the larger of the two
     // weights [layers][2][k][k], their gradient and Adam moments
     int wl = 0, wk = 0;
     bool have_weights = false;
     DevBuf<float> W, gW, mW, vW, wpart;
     // work: E_0, then per layer S, Z, D [N, k] and ss [N]; F and dLoss / dF [N, (layers + 1) k]; the backward pass's rows
-    DevBuf<float> E0, S, Z, D, ss, F, G, gD, gZ, gS, coef;
-    DevBuf<double> loss;
-    DevBuf<int64_t> seg_ptr, seg_row;
-    DevBuf<int32_t> ent;
-    std::vector<double> h_loss;
-    std::vector<std::pair<int64_t, int32_t>> h_ents;
-    std::vector<int64_t> h_seg_ptr, h_seg_row;
-    std::vector<int32_t> h_ent;
-    // time stamps: event t closes an interval that belongs to phase stamp_phase[t]
-    std::vector<hipEvent_t> ev;
-    std::vector<int> stamp_phase;
-    size_t stamps = 0;
+    DevBuf<float> E0, S, Z, D, ss, F, G, gD, gZ, gS;
+    gcn::Batch batch;
+    gcn::PhaseTimer timer;
 };
 
 namespace {
+
+enum { kGather = 0, kDense = 1, kBatch = 2, kBackward = 3, kWgrad = 4, kAdam = 5, kPhases = 6 };
 
 struct Run {                                         // what one call propagates with
     int L, training;
@@ -71,56 +44,7 @@ int ngcf_new(yue_ctx *c) {
     return YUE_OK;
 }
 
-template <typename T>
-int upload(DevBuf<T> &buf, const T *src, int64_t count) {
-    HIPCHK(buf.resize((size_t)std::max<int64_t>(count, 1)));
-    if (count > 0) HIPCHK(hipMemcpy(buf.p, src, (size_t)count * sizeof(T), hipMemcpyHostToDevice));
-    return YUE_OK;
-}
-
-int stamp(yue_ctx *c, yue_ngcf *s, int phase) {
-    if (s->stamps == s->ev.size()) {
-        hipEvent_t e = nullptr;
-        HIPCHK(hipEventCreate(&e));
-        s->ev.push_back(e); s->stamp_phase.push_back(0);
-    }
-    s->stamp_phase[s->stamps] = phase;
-    HIPCHK(hipEventRecord(s->ev[s->stamps++], c->stream));
-    return YUE_OK;
-}
-
-int read_times(yue_ctx *c, yue_ngcf *s) {
-    for (int p = 0; p < kPhases; ++p) c->ngcf_ns[p] = 0;
-    for (size_t t = 1; t < s->stamps; ++t) {
-        float ms = 0.0f;
-        HIPCHK(hipEventElapsedTime(&ms, s->ev[t - 1], s->ev[t]));
-        c->ngcf_ns[s->stamp_phase[t]] += (int64_t)(1e6 * (double)ms);
-    }
-    return YUE_OK;
-}
-
-int build_hubs(Csr &g, int64_t N, int64_t thr) {
-    if (g.hub_built == thr) return YUE_OK;
-    std::vector<int64_t> hub_row, hub_part_ptr{0}, part_beg, part_end;
-    int64_t light = 0;
-    for (int64_t r = 0; r < N; ++r) {
-        const int64_t b = g.h_ptr[(size_t)r], e = g.h_ptr[(size_t)r + 1];
-        if (e - b <= thr) { light += e - b; continue; }
-        for (int64_t p = b; p < e; p += thr) { part_beg.push_back(p); part_end.push_back(std::min(p + thr, e)); }
-        hub_row.push_back(r);
-        hub_part_ptr.push_back((int64_t)part_beg.size());
-    }
-    g.H = (int64_t)hub_row.size(); g.parts = (int64_t)part_beg.size();
-    if (g.parts >= INT32_MAX) return fail(YUE_ERR_ARG, "yue_ngcf: ngcf_hub cuts the hub rows into 2^31 parts or more");
-    int rc;
-    if ((rc = upload(g.hub_row, hub_row.data(), g.H)) || (rc = upload(g.hub_part_ptr, hub_part_ptr.data(), g.H + 1)) ||
-        (rc = upload(g.part_beg, part_beg.data(), g.parts)) || (rc = upload(g.part_end, part_end.data(), g.parts)))
-        return rc;
-    const int64_t mean = std::max<int64_t>(1, light / std::max<int64_t>(1, N - g.H));     // as lgcn_host.hip sizes a wave's rows
-    g.rpw = (int)std::min<int64_t>(16, std::max<int64_t>(1, 64 / mean));
-    g.hub_built = thr;
-    return YUE_OK;
-}
+int stamp(yue_ctx *c, yue_ngcf *s, int phase) { return gcn::stamp(c, s->timer, phase); }
 
 int ngcf_ready(yue_ctx *c, yue_ngcf **out, int layers, double keep, const char *who) {
     const std::string w(who);
@@ -142,32 +66,21 @@ int ngcf_ready(yue_ctx *c, yue_ngcf **out, int layers, double keep, const char *
                                      std::to_string(layers) + " at k " + std::to_string(c->k));
     HIPCHK(hipSetDevice(c->device));
     int rc;
-    if ((rc = build_hubs(s->A, s->m + s->n, c->opt_ngcf_hub)) || (rc = build_hubs(s->At, s->m + s->n, c->opt_ngcf_hub))) return rc;
+    if ((rc = gcn::build_hubs(s->A, s->m + s->n, c->opt_ngcf_hub, "yue_ngcf: ngcf_hub")) ||
+        (rc = gcn::build_hubs(s->At, s->m + s->n, c->opt_ngcf_hub, "yue_ngcf: ngcf_hub")))
+        return rc;
     c->ngcf_hubs = s->A.H + s->At.H; c->ngcf_parts = s->A.parts + s->At.parts;
     HIPCHK(s->partial.resize((size_t)std::max<int64_t>(1, std::max(s->A.parts, s->At.parts) * c->k)));
-    s->stamps = 0;
+    s->timer.stamps = 0;
     *out = s;
     return YUE_OK;
 }
 
 // out = base + M X (base may be null, out may be base); rows below m to outU, the others to outV
-int product(yue_ctx *c, yue_ngcf *s, const Csr &g, const float *X, const float *base, float *outU, float *outV) {
-    yue::LgcnArgs a{};
-    a.ptr = g.ptr.p; a.col = g.col.p; a.w = g.w.p; a.X = X; a.N = s->m + s->n; a.m = s->m; a.k = c->k; a.rpw = g.rpw; a.gather = 1;
-    a.hub = g.hub_built;
-    a.hub_row = g.hub_row.p; a.hub_part_ptr = g.hub_part_ptr.p; a.part_beg = g.part_beg.p; a.part_end = g.part_end.p;
-    a.partial = s->partial.p; a.H = g.H; a.parts = g.parts;
-    const int64_t waves = (a.N + a.rpw - 1) / a.rpw;
-    with_kr(c->k, [&](auto kr) {
-        constexpr int KR = kr() > 2 ? 2 : kr();
-        hipLaunchKernelGGL((yue::k_ngcf_rows<KR>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, c->stream, a, base, outU, outV);
-        if (g.H > 0) {
-            hipLaunchKernelGGL((yue::k_lgcn_hub_parts<KR>), dim3((unsigned)((g.parts + 3) / 4)), dim3(256), 0, c->stream, a);
-            hipLaunchKernelGGL((yue::k_ngcf_hub_combine<KR>), dim3((unsigned)((g.H + 3) / 4)), dim3(256), 0, c->stream, a, base, outU, outV);
-        }
-    });
-    HIPCHK(hipGetLastError());
-    return YUE_OK;
+int product(yue_ctx *c, yue_ngcf *s, const gcn::Graph &g, const float *X, const float *base, float *outU, float *outV) {
+    yue::LgcnArgs a = gcn::graph_args(g, s->m + s->n, s->m, c->k, s->partial.p);
+    a.X = X; a.base = base; a.outU = outU; a.outV = outV;
+    return gcn::launch_product<yue::kLgcnPlain>(c, g, a);
 }
 
 yue::NgcfLayerArgs layer_args(const yue_ctx *c, const yue_ngcf *s, const Run &r, int l) {
@@ -247,61 +160,18 @@ int backward(yue_ctx *c, yue_ngcf *s, const Run &r) {
     return YUE_OK;
 }
 
-int check_batch(yue_ctx *c, const int32_t *u, const int32_t *i, const int32_t *j, int64_t T, const char *who) {
-    if (T < 1 || T >= (1ll << 29) || !u || !i || !j) return fail(YUE_ERR_ARG, std::string(who) + ": needs 1 <= T < 2^29 and the three id arrays");
-    for (int64_t t = 0; t < T; ++t)
-        if (u[t] < 0 || u[t] >= c->m || i[t] < 0 || i[t] >= c->n || j[t] < 0 || j[t] >= c->n)
-            return fail(YUE_ERR_ARG, std::string(who) + ": triplet " + std::to_string(t) + " out of range");
-    return YUE_OK;
-}
-
 // forward, minibatch (LightGCN's kernels at width (layers + 1) k), backward: the loss, the gradients in dP / dQ / gW
 int gradient(yue_ctx *c, yue_ngcf *s, const Run &r, const int32_t *u, const int32_t *i, const int32_t *j, int64_t T, double reg, double *loss_out) {
     const int64_t N = s->m + s->n;
     const int width = (r.L + 1) * c->k;
-    int rc = yue_host::upload_triplets(c, u, i, j, T, true);
-    if (rc) return rc;
-    // the 3 T (row of F, triplet, role) entries by row, a row's entries in triplet order: the order k_lgcn_batch_g adds in
-    std::vector<std::pair<int64_t, int32_t>> &ents = s->h_ents;
-    std::vector<int64_t> &seg_ptr = s->h_seg_ptr, &seg_row = s->h_seg_row;
-    std::vector<int32_t> &ent = s->h_ent;
-    ents.resize((size_t)(3 * T)); ent.resize((size_t)(3 * T)); seg_ptr.clear(); seg_row.clear();
-    for (int64_t t = 0; t < T; ++t) {
-        ents[(size_t)(3 * t)] = {u[t], (int32_t)(4 * t)};
-        ents[(size_t)(3 * t + 1)] = {s->m + i[t], (int32_t)(4 * t + 1)};
-        ents[(size_t)(3 * t + 2)] = {s->m + j[t], (int32_t)(4 * t + 2)};
-    }
-    std::sort(ents.begin(), ents.end());
-    for (int64_t p = 0; p < 3 * T; ++p) {
-        if (p == 0 || ents[(size_t)p].first != ents[(size_t)p - 1].first) { seg_ptr.push_back(p); seg_row.push_back(ents[(size_t)p].first); }
-        ent[(size_t)p] = ents[(size_t)p].second;
-    }
-    const int64_t S = (int64_t)seg_row.size();
-    seg_ptr.push_back(3 * T);
-    HIPCHK(hipStreamSynchronize(c->stream));             // (the blocking uploads below overwrite what an earlier call's kernels read)
-    if ((rc = upload(s->seg_ptr, seg_ptr.data(), S + 1)) || (rc = upload(s->seg_row, seg_row.data(), S)) || (rc = upload(s->ent, ent.data(), 3 * T))) return rc;
-    HIPCHK(s->coef.resize((size_t)T)); HIPCHK(s->loss.resize((size_t)T)); HIPCHK(s->G.resize((size_t)(N * width)));
-
+    int rc;
+    if ((rc = gcn::batch_prepare(c, s->batch, s->m, u, i, j, T))) return rc;
+    HIPCHK(s->G.resize((size_t)(N * width)));
     if ((rc = forward(c, s, r))) return rc;
     HIPCHK(hipMemsetAsync(s->G.p, 0, (size_t)(N * width) * sizeof(float), c->stream));
-    yue::LgcnBatchArgs b{};
-    b.F = s->F.p; b.G = s->G.p; b.m = s->m; b.k = width; b.u = c->xu.p; b.i = c->xi.p; b.j = c->xj.p; b.T = T; b.S = S; b.reg = (float)reg;
-    b.c = s->coef.p; b.loss = s->loss.p; b.seg_ptr = s->seg_ptr.p; b.seg_row = s->seg_row.p; b.ent = s->ent.p;
-    with_kr(width, [&](auto kr) {
-        constexpr int KR = kr();
-        hipLaunchKernelGGL((yue::k_lgcn_batch_y<KR>), dim3((unsigned)((T + 3) / 4)), dim3(256), 0, c->stream, b);
-        hipLaunchKernelGGL((yue::k_lgcn_batch_g<KR>), dim3((unsigned)((S + 3) / 4)), dim3(256), 0, c->stream, b);
-    });
-    HIPCHK(hipGetLastError());
-    if ((rc = stamp(c, s, kBatch))) return rc;
+    if ((rc = gcn::batch_launch(c, s->batch, s->F.p, s->G.p, s->m, width, T, reg)) || (rc = stamp(c, s, kBatch))) return rc;
     if ((rc = backward(c, s, r))) return rc;
-    s->h_loss.resize((size_t)T);
-    HIPCHK(hipMemcpyAsync(s->h_loss.data(), s->loss.p, (size_t)T * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    double loss = 0.0;
-    for (int64_t t = 0; t < T; ++t) loss += s->h_loss[(size_t)t];      // triplet order
-    if (loss_out) *loss_out = loss;
-    return YUE_OK;
+    return gcn::batch_loss(c, s->batch, T, loss_out);
 }
 
 Run make_run(int layers, int training, double keep, uint64_t seed, int64_t step) {
@@ -320,9 +190,8 @@ void ngcf_release(yue_ctx *c) {
     s->A.release(); s->At.release(); s->partial.release();
     s->W.release(); s->gW.release(); s->mW.release(); s->vW.release(); s->wpart.release();
     s->E0.release(); s->S.release(); s->Z.release(); s->D.release(); s->ss.release(); s->F.release(); s->G.release();
-    s->gD.release(); s->gZ.release(); s->gS.release(); s->coef.release(); s->loss.release();
-    s->seg_ptr.release(); s->seg_row.release(); s->ent.release();
-    for (auto &e : s->ev) if (e) (void)hipEventDestroy(e);
+    s->gD.release(); s->gZ.release(); s->gS.release();
+    s->batch.release(); s->timer.release();
     delete s;
     c->ngcf = nullptr;
 }
@@ -423,7 +292,7 @@ int yue_ngcf_propagate(yue_ctx *c, int layers, int training, double keep, uint64
     if (D_out) HIPCHK(hipMemcpyAsync(D_out, s->D.p, layer_bytes, hipMemcpyDeviceToHost, c->stream));
     if (F_out) HIPCHK(hipMemcpyAsync(F_out, s->F.p, N * (size_t)(layers + 1) * k * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    return read_times(c, s);
+    return gcn::read_times(s->timer, c->ngcf_ns, kPhases);
 }
 
 int yue_ngcf_grad(yue_ctx *c, int layers, int training, double keep, uint64_t seed, int64_t step, const int32_t *u, const int32_t *i, const int32_t *j,
@@ -432,7 +301,7 @@ int yue_ngcf_grad(yue_ctx *c, int layers, int training, double keep, uint64_t se
     int rc = ngcf_ready(c, &s, layers, keep, "yue_ngcf_grad");
     if (rc) return rc;
     if (step < 0) return fail(YUE_ERR_ARG, "yue_ngcf_grad: needs step >= 0");
-    if ((rc = check_batch(c, u, i, j, T, "yue_ngcf_grad"))) return rc;
+    if ((rc = gcn::check_batch(c, u, i, j, T, "yue_ngcf_grad"))) return rc;
     if ((rc = gradient(c, s, make_run(layers, training, keep, seed, step), u, i, j, T, reg, loss_out))) return rc;
     const size_t mk = (size_t)(c->m * c->k), nk = (size_t)(c->n * c->k);
     if (gU_out) HIPCHK(hipMemcpy(gU_out, c->dP.p, mk * sizeof(float), hipMemcpyDeviceToHost));
@@ -441,7 +310,7 @@ int yue_ngcf_grad(yue_ctx *c, int layers, int training, double keep, uint64_t se
     // dP / dQ are the cleared gradient buffers of yue_adam_step: hand them back as that call expects them
     HIPCHK(hipMemsetAsync(c->dP.p, 0, mk * sizeof(float), c->stream)); HIPCHK(hipMemsetAsync(c->dQ.p, 0, nk * sizeof(float), c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    return read_times(c, s);
+    return gcn::read_times(s->timer, c->ngcf_ns, kPhases);
 }
 
 int yue_ngcf_step(yue_ctx *c, int layers, int training, double keep, uint64_t seed, const int32_t *u, const int32_t *i, const int32_t *j, int64_t T,
@@ -449,7 +318,7 @@ int yue_ngcf_step(yue_ctx *c, int layers, int training, double keep, uint64_t se
     yue_ngcf *s = nullptr;
     int rc = ngcf_ready(c, &s, layers, keep, "yue_ngcf_step");
     if (rc) return rc;
-    if ((rc = check_batch(c, u, i, j, T, "yue_ngcf_step"))) return rc;
+    if ((rc = gcn::check_batch(c, u, i, j, T, "yue_ngcf_step"))) return rc;
     if (step < 1) return fail(YUE_ERR_ARG, "yue_ngcf_step: needs step >= 1");
     if (c->adam_m != c->m || c->adam_n != c->n || c->adam_k != c->k) { if ((rc = yue_adam_reset(c))) return rc; }
     if ((rc = gradient(c, s, make_run(layers, training, keep, seed, step), u, i, j, T, reg, loss_out))) return rc;
@@ -457,7 +326,7 @@ int yue_ngcf_step(yue_ctx *c, int layers, int training, double keep, uint64_t se
     if ((rc = yue_host::adam_apply_dense(c, s->W.p, s->mW.p, s->vW.p, s->gW.p, (int64_t)layers * 2 * c->k * c->k, lr, step))) return rc;
     if ((rc = stamp(c, s, kAdam))) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
-    return read_times(c, s);
+    return gcn::read_times(s->timer, c->ngcf_ns, kPhases);
 }
 
 }  // extern "C"

@@ -1,10 +1,9 @@
-// NGCF kernels for gfx950 (reference recommender/advanced/NGCF.py).  The sparse-times-dense gather is
-// LightGCN's (lgcn_kernels.hpp: lgcn_gather, k_lgcn_hub_parts, unchanged) with a plain epilogue; new here is the dense half of
-// a layer on v_mfma_f32_32x32x2_f32, forward and backward, and the weight gradients.  Everything float32; no atomics: every
-// output element has one writer and every sum a fixed order, so two runs on the same input give the same bits.
+// NGCF kernels for gfx950 (reference recommender/advanced/NGCF.py).  The sparse-times-dense products
+// and the minibatch are lgcn_kernels.hpp's (k_lgcn_rows / k_lgcn_hub_parts / k_lgcn_hub_combine with the plain epilogue,
+// k_lgcn_batch_y / k_lgcn_batch_g at width (layers + 1) k), launched through gcn_host.hpp; here is the dense half of a layer
+// on v_mfma_f32_32x32x2_f32, forward and backward, and the weight gradients.  Everything float32; no atomics: every output
+// element has one writer and every sum a fixed order, so two runs on the same input give the same bits.
 //
-//   k_ngcf_rows / k_ngcf_hub_combine   out[row] = base[row] + sum_j w_j X[col_j]  (base may be null; rows < m go to outU, the
-//                     others to outV, so the last backward product writes g[U;V] into the two gradient buffers)
 //   k_ngcf_layer_fwd  a workgroup takes 32 rows: [S + E | E o S] (32 x 2 KP, KP = k rounded up to 32, zero padded) in LDS times
 //                     [W_1; W_2] from global memory.  Z[row][c] is ONE chain of fused multiply-adds from 0: j = 0 .. k-1 over
 //                     (S + E)[j] W_1[j][c], then j = 0 .. k-1 over (E o S)[j] W_2[j][c]  (the padded terms add 0 * 0).
@@ -37,54 +36,6 @@ __host__ __device__ inline bool ngcf_keep(uint64_t seed, uint64_t step, int laye
 }
 
 typedef float ngcf_f32x16 __attribute__((ext_vector_type(16)));
-
-// ---- gather -------------------------------------------------------------------------------------------------------------
-template <int KR>
-__device__ __forceinline__ void ngcf_gather_out(const LgcnArgs &a, int64_t row, int lane, const float (&acc)[KR], const float *base, float *outU,
-                                                float *outV) {
-    const int k = a.k;
-    float *dst = row < a.m ? outU + row * k : outV + (row - a.m) * k;
-#pragma unroll
-    for (int r = 0; r < KR; ++r) {
-        const int el = 64 * r + lane;
-        if (el < k) dst[el] = (base ? base[row * k + el] : 0.0f) + acc[r];
-    }
-}
-
-template <int KR>
-__global__ void __launch_bounds__(256) k_ngcf_rows(LgcnArgs a, const float *base, float *outU, float *outV) {
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int64_t r0 = wave * a.rpw;
-    const int64_t r1 = r0 + a.rpw < a.N ? r0 + a.rpw : a.N;
-    for (int64_t row = r0; row < r1; ++row) {
-        const int64_t b = a.ptr[row], e = a.ptr[row + 1];
-        if (e - b > a.hub) continue;                                 // k_lgcn_hub_parts / k_ngcf_hub_combine
-        float acc[KR];
-#pragma unroll
-        for (int r = 0; r < KR; ++r) acc[r] = 0.0f;
-        lgcn_gather<KR>(a, b, e, lane, acc);
-        ngcf_gather_out<KR>(a, row, lane, acc, base, outU, outV);
-    }
-}
-
-template <int KR>
-__global__ void __launch_bounds__(256) k_ngcf_hub_combine(LgcnArgs a, const float *base, float *outU, float *outV) {
-    const int lane = threadIdx.x & 63;
-    const int64_t h = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (h >= a.H) return;
-    float acc[KR];
-#pragma unroll
-    for (int r = 0; r < KR; ++r) acc[r] = 0.0f;
-    for (int64_t p = a.hub_part_ptr[h]; p < a.hub_part_ptr[h + 1]; ++p) {
-#pragma unroll
-        for (int r = 0; r < KR; ++r) {
-            const int el = 64 * r + lane;
-            acc[r] = acc[r] + (el < a.k ? a.partial[p * a.k + el] : 0.0f);
-        }
-    }
-    ngcf_gather_out<KR>(a, a.hub_row[h], lane, acc, base, outU, outV);
-}
 
 // ---- the dense half of a layer ------------------------------------------------------------------------------------------
 struct NgcfLayerArgs {
