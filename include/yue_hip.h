@@ -42,6 +42,7 @@ typedef struct yue_ctx yue_ctx;
 #define YUE_ERR_HIP        -2   /* HIP runtime error */
 #define YUE_ERR_FEW_ITEMS  -3   /* a user has fewer than N candidates (reference: IndexError) */
 #define YUE_ERR_COMM       -4   /* RCCL error */
+#define YUE_ERR_SATURATED  -5   /* yue_cdae_step: a sampled output rounds to 1.0f; nothing was updated */
 
 #define YUE_MAX_ATTEMPTS   64   /* negative-sampler attempts before a triplet is skipped */
 #define YUE_UNIQUE_ID_BYTES 128
@@ -547,6 +548,50 @@ int yue_ngcf_grad(yue_ctx *ctx, int layers, int training, double keep, uint64_t 
                   const int32_t *j, int64_t T, double reg, double *loss_out, float *gU_out, float *gV_out, float *gW_out);
 int yue_ngcf_step(yue_ctx *ctx, int layers, int training, double keep, uint64_t seed, const int32_t *u, const int32_t *i, const int32_t *j,
                   int64_t T, double lr, double reg, int64_t step, double *loss_out);
+
+/* CDAE (reference recommender/advanced/CDAE.py): a denoising autoencoder over the item axis, worked as
+ * sparse-in / sampled-out.  The five variables live in a state of their own (not the factors of yue_set_factors): U [m][h],
+ * encoder W [n][h], decoder W' [h][n] (kept transposed on the device), b [h], b' [n], each with Adam moments.
+ *   A batch is B slots: users[B] (a user may repeat) and per slot the sampled items as a CSR (sample_ptr [B + 1], sample_items
+ *   ascending and distinct within a slot).  The input row of a slot holds the user's event counts c at the user's items.
+ *   Input entry (slot, item) of `step` is KEPT when the top 24 bits of hash(seed ^ 0x43444145, step, slot, item, 0) lie below
+ *   floor(co * 2^24); the hash is the user-network stage's counter hash.
+ *   hid = sigmoid(sum over kept entries of c W[item] + b + U[u]);  logit = hid . W'[:, item] + b'[item] at the sampled entries;
+ *   y_pred = max(1e-6, sigmoid(logit));  y_true = c where the item is a kept input entry of the slot, else 0.
+ *   loss = (sum over sampled entries of -y_true log y_pred - (1 - y_true) log(1 - y_pred) + (B n - entries) * -log(1 - 1e-6))
+ *          / (B n) + reg / 2 (|W|^2 + |W'|^2 + |b|^2 + |b'|^2 + sum over slots |U[u]|^2).
+ *   yue_cdae_set_data     the user CSR: ptr [m + 1], items ascending and distinct within a user, counts >= 1.
+ *   yue_cdae_set_params   U, W, W' [h][n], b, b' for the data's m and n; clears the moments.
+ *   yue_cdae_get_params   params / m_out / v_out: each NULL or five pointers (U, W, W' [h][n], b, b'; any may be NULL).
+ *   yue_cdae_forward      hid_out [B][h], kept_out (one flag per input entry, slot by slot in the user's item order),
+ *                         logit_out and ypred_out per sampled entry, the loss (any output may be NULL).
+ *   yue_cdae_grad         the loss and the five gradients, dense, in the shapes of set_params; no step (outputs may be NULL).
+ *                         A sampled entry whose y_pred equals 1.0f is counted, makes the loss inf and contributes no gradient.
+ *   yue_cdae_step         the same gradients, then Adam (beta 0.9 / 0.999, eps 1e-8, lr_t of `step` = 1, 2, ...) on EVERY row of
+ *                         all five variables (TF-1 applies Adam densely: moments decay and rows move with a zero gradient).
+ *                         When a sampled y_pred equals 1.0f the loss is returned as inf, nothing is updated and the call
+ *                         returns YUE_ERR_SATURATED (option "cdae_last_saturated": how many).
+ *   yue_cdae_load_factors encodes all m users with a mask of ones and fills the context's factor matrices on the device with
+ *                         P[u] = [hid(u) | 1], Q[i] = [W'[:, i] | b'[i]] (k = h + 1), as yue_set_factors would: yue_scores,
+ *                         yue_topn_scan and yue_get_factors then serve the decoder's logits (upload the interactions again).
+ *   yue_cdae_times        ns_out [4]: device time of the last call's encode, decode, regroup and adam phases.
+ * Refused with YUE_ERR_ARG before any launch: h outside 1 .. 128, B < 1, an id out of range, a slot's items not ascending and
+ * distinct, co outside (0, 1], no data or no parameters.  Every sum has a fixed order (items ascending, slots ascending) and no
+ * atomic is used: two calls on the same input return the same bits.  Option "cdae_hub" (default 1024, inherited from "lgcn_hub"):
+ * encoder rows and regrouped segments with more entries are cut into parts of that many, one wave per part, combined in
+ * ascending order.  Read-only options "cdae_last_hubs", "cdae_last_parts", "cdae_last_saturated".
+ */
+int yue_cdae_set_data(yue_ctx *ctx, int64_t m, int64_t n, const int64_t *ptr, const int32_t *items, const int32_t *counts);
+int yue_cdae_set_params(yue_ctx *ctx, int h, const float *U, const float *W, const float *Wd, const float *b, const float *bd);
+int yue_cdae_get_params(yue_ctx *ctx, float *const *params, float *const *m_out, float *const *v_out);
+int yue_cdae_forward(yue_ctx *ctx, const int32_t *users, int64_t B, const int64_t *sample_ptr, const int32_t *sample_items, double co, uint64_t seed,
+                     int64_t step, double reg, float *hid_out, int32_t *kept_out, float *logit_out, float *ypred_out, double *loss_out);
+int yue_cdae_grad(yue_ctx *ctx, const int32_t *users, int64_t B, const int64_t *sample_ptr, const int32_t *sample_items, double co, uint64_t seed,
+                  int64_t step, double reg, double *loss_out, float *gU_out, float *gW_out, float *gWd_out, float *gb_out, float *gbd_out);
+int yue_cdae_step(yue_ctx *ctx, const int32_t *users, int64_t B, const int64_t *sample_ptr, const int32_t *sample_items, double co, uint64_t seed,
+                  double lr, double reg, int64_t step, double *loss_out);
+int yue_cdae_load_factors(yue_ctx *ctx);
+int yue_cdae_times(yue_ctx *ctx, int64_t *ns_out);
 
 /* Multi-GPU (one process per GPU, RCCL over xGMI).  Rank 0 creates the id, the caller ships
  * the 128 bytes to the other ranks (any side channel), every rank calls yue_comm_init. */

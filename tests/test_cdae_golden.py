@@ -1,0 +1,319 @@
+"""CPU: the CDAE contract (tests/helpers/numpy_cdae.py) against its goldens (tools/make_cdae_goldens.py; they
+pin the contract, not TensorFlow, which cannot run here), its hand-derived backward pass against central differences in fp64, the
+host mask's properties, the plugin's sampler on a recorded log, the conditioning statement of every GPU case, the plugin on a
+stubbed device with its refusals, and the end-to-end logs on the float32 contract."""
+import json
+import os
+import random
+
+import numpy as np
+import pytest
+
+from helpers import cdae_cases as cc
+from helpers import cdae_e2e as ce
+from helpers import numpy_cdae as cd
+from helpers import numpy_cune_net as ncn
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def golden(tag):
+    return json.load(open(os.path.join(ROOT, 'tests', 'golden', 'g20_cdae_%s.json' % tag)))
+
+
+@pytest.mark.parametrize('name', ['h33', 'twice', 'low', 'keep01'])
+def test_contract_reproduces_the_goldens(name):
+    z, c = golden(name), cc.build(name)
+    assert z['seed'] == c['seed'] and z['entries'] == int(c['sptr'][-1]) and z['kept'] == sum(int(f.sum()) for f in c['fw']['flags'])
+    assert abs(c['loss'] - z['loss']) <= 1e-12 * abs(z['loss'])
+    for key, a in [('hid', c['fw']['hid']), ('logit', c['fw']['logit'])] + [('g' + k, c['g'][k]) for k in cd.NAMES]:
+        a = np.asarray(a, np.float64)
+        assert np.allclose([a.sum(), np.abs(a).sum()], z[key], rtol=1e-11, atol=1e-13), key
+    # the float32 figures depend on the library's float32 kernels to the last bit: the same size, not the same bits
+    assert abs(c['loss32'] - z['loss32']) <= 4 * 2.0 ** -24 * abs(z['loss'])
+    for k, v in z['d32'].items():
+        assert c['d32'][k] <= 4 * v + 2.0 ** -24, k
+
+
+def _tiny():
+    rs = np.random.RandomState(1)
+    m, n, h = 5, 7, 3
+    ev_u, ev_t = [0, 0, 1, 1, 1, 2, 3, 3, 3, 4, 4], [1, 1, 2, 3, 3, 0, 6, 5, 5, 4, 1]
+    data = cd.user_csr(ev_u, ev_t, m)
+    p = {k: v.astype(np.float64) for k, v in cd.init_params(rs, m, n, h, 0.5).items()}
+    users = [1, 3, 1, 4]                                             # B = 4, user 1 twice
+    sptr, sitems = cd.sample_csr([{2, 3, 5}, {5, 6, 0, 1}, {2, 3, 6}, {1, 4, 2}])
+    return p, (data, users, sptr, sitems, 0.6, 5, 2, 0.05)
+
+
+def test_backward_matches_central_differences_in_fp64():
+    p, args = _tiny()
+    loss, g, fw = cd.loss_and_grad(p, *args)
+    flags = np.concatenate(fw['flags'])
+    assert flags.any() and not flags.all() and fw['y_true'].max() == 2 and np.abs(fw['logit']).max() < 10
+    h, worst = 1e-5, 0.0
+    for k in cd.NAMES:
+        X = p[k]
+        for idx in np.ndindex(X.shape):                              # every element of every variable
+            old = X[idx]
+            X[idx] = old + h
+            lp = cd.loss_and_grad(p, *args)[0]
+            X[idx] = old - h
+            lm = cd.loss_and_grad(p, *args)[0]
+            X[idx] = old
+            fd = (lp - lm) / (2 * h)
+            worst = max(worst, abs(fd - g[k][idx]) / max(1e-3, abs(fd)))
+    print('worst relative difference %.3g' % worst, 'loss', float(loss))
+    # central differences at step h: truncation h^2 / 6 |f'''| with |f'''| <= 10 here (a sigmoid's derivatives are below 1, weights
+    # below 1.5, counts at most 2): 1.7e-10; rounding: the loss (below 2) is known to some 10 ulps of 2^-52, divided by 2 h: 2.2e-10;
+    # together 4e-10 over the 1e-3 floor of the denominators: 4e-7
+    assert worst <= 1e-6
+
+
+def test_mask_is_a_pure_function_and_keeps_the_asked_share():
+    items = np.arange(50)
+    a, b = cd.mask_bits(7, 3, 1, items), cd.mask_bits(7, 3, 1, items)
+    assert np.array_equal(a, b) and a.min() >= 0 and a.max() < 1 << 24
+    for item in (0, 13, 49):                                         # element by element the counter hash of the user-network stage
+        assert int(a[item]) == ncn.cnet_hash(7 ^ cd.TAG, 3, 1, item, 0) >> 40
+    for other in (cd.mask_bits(8, 3, 1, items), cd.mask_bits(7, 4, 1, items), cd.mask_bits(7, 3, 2, items)):
+        assert not np.array_equal(a, other)                          # seed, step, slot: two slots with one user get other masks
+    assert np.array_equal(cd.mask_bits(7, 3, 1, np.arange(60))[:50], a)
+    assert cd.kept(7, 3, 1, items, 1.0).all()
+    for co in (0.1, 0.5):
+        flags = np.concatenate([cd.kept(11, 1, slot, np.arange(2000), co) for slot in range(128)])
+        share, sd = flags.mean(), np.sqrt(co * (1 - co) / flags.size)
+        print('co', co, 'kept share %.5f' % share, 'in standard deviations %.2f' % ((share - co) / sd))
+        assert abs(share - co) <= 4 * sd
+
+
+def _plugin(tmp_path, events, conf_edits=(), test=None):
+    from yue_amd.recommender.advanced.CDAE import CDAE
+    from yue_amd.tool.config import Config
+    log = tmp_path / 'log.txt'
+    log.write_text(''.join('%010d,u%d,t%d,a0\n' % (t, u, i) for t, (u, i) in enumerate(events)))
+    text = open(os.path.join(ROOT, 'config', 'CDAE.conf')).read()
+    text = text.replace('record=./dataset/log.txt', 'record=%s' % log).replace(' -byTime 0.2', '')
+    for old, new in conf_edits:
+        assert old in text, old
+        text = text.replace(old, new)
+    path = tmp_path / 'CDAE.conf'
+    path.write_text(text)
+    train = [{'user': 'u%d' % u, 'track': 't%d' % i, 'artist': 'a0', 'time': str(t)} for t, (u, i) in enumerate(events)]
+    return CDAE(Config(str(path)), train, [dict(train[0])] if test is None else test)
+
+
+def test_next_batch_on_a_fixed_log_and_seed_gives_the_recorded_users_and_sample_sets(tmp_path, capsys):
+    z = golden('sampler')
+    rec = _plugin(tmp_path, list(zip(z['ev_u'], z['ev_t'])), [('CDAE=-batch_size 256', 'CDAE=-batch_size %d' % z['batch_size'])])
+    rec.readConfiguration()
+    np.random.seed(3)
+    rec.initModel()
+    assert (rec.m, rec.n, rec.negative_sp, rec.batch_size) == (z['m'], z['n'], z['neg'], z['batch_size'])
+    data = cd.user_csr(z['ev_u'], z['ev_t'], z['m'])
+    for got, want in zip(rec._user_csr, data):
+        assert np.array_equal(got, want)
+    assert rec._user_csr[2].max() >= 2                                # counts, not 0 / 1
+    random.seed(z['sampler_seed'])
+    for users, sets in z['batches']:
+        got_u, got_s = rec.next_batch()
+        assert got_u == users and [sorted(s) for s in got_s] == sets
+    # the start values: creation order U, W, W', b, b', after the base class's P and Q
+    rs = np.random.RandomState(3)
+    rs.rand(z['m'], rec.k); rs.rand(z['n'], rec.k)
+    p = cd.init_params(rs, z['m'], z['n'], 128, 0.25)
+    for k, v in ce.params(rec).items():
+        assert np.array_equal(v, p[k]), k
+    assert np.abs(rec.U).max() <= np.sqrt(6.0 / (z['m'] + 128))
+
+
+@pytest.mark.parametrize('name', cc.GPU_CASES)
+def test_every_gpu_case_reaches_its_branch_and_meets_its_conditioning_statement(name):
+    c = cc.build(name)
+    print(name, 'max |logit| %.3g' % c['logit_max'], 'special', c['special_logits'][:3], ' '.join('%s %.3g' % kv for kv in sorted(c['d32'].items())))
+    assert c['logit_max'] <= 10                                      # no output near 1 or near the clamp
+    assert max(c['d32'].values()) <= 1e-6
+    ptr, items, cnt = c['data']
+    fw, users, sets, n = c['fw'], c['users'], c['sets'], c['n']
+    assert {0, n - 1} <= sets[0] and cnt.max() == 3                  # both ends of the item axis; counts up to 3
+    for s, u in enumerate(users):
+        assert set(items[ptr[u]:ptr[u + 1]].tolist()) <= sets[s]
+    if c['special'] in ('low', 'sat'):
+        sp = c['special_logits']
+        assert len(sp) == c['B'] and (np.abs(sp - (-20 if c['special'] == 'low' else 40)) < 1).all()       # far across the line
+        assert (c['saturated'] == c['B']) == (c['special'] == 'sat')
+        if c['special'] == 'low':
+            at = fw['col'] == cc.SPECIAL
+            assert (fw['dec'][at] < cd.CLAMP / 100).all() and (fw['y_pred'][at] == cd.CLAMP).all() and (fw['e'][at] == 0).all()
+    else:
+        assert c['saturated'] == 0
+    if c['special'] == 'twice':
+        assert users[0] == users[1] and not np.array_equal(fw['flags'][0], fw['flags'][1])
+    if c['special'] == 'empty':
+        assert ptr[1] == ptr[0] and users[0] == 0 and len(sets[0] - {0, n - 1}) == 0       # a user with no items at all
+        assert len(fw['flags'][1]) == 1 and not fw['flags'][1].any()                        # a slot whose only input is dropped
+    if c['special'] == 'hub':
+        hubs, parts = cd.hub_counts(c['data'], users, c['sptr'], c['sitems'], cc.HUB)
+        assert users[0] == 1 and ptr[2] - ptr[1] == 40 and all(cc.SPECIAL in s for s in sets) and c['B'] > cc.HUB and hubs >= 3 and parts >= 5 + 2 + 2
+    if c['co'] == 1.0:
+        assert all(f.all() for f in fw['flags'])
+    elif c['special'] != 'empty' and c['B'] > 1:
+        flags = np.concatenate(fw['flags'])
+        assert flags.any() and not flags.all()
+    if name in ('h33', 'keep01', 'big'):
+        assert fw['y_true'].max() > 1                               # a kept count above 1
+        ins = np.concatenate([items[ptr[u]:ptr[u + 1]] for u in users])
+        flags = np.concatenate(fw['flags'])
+        assert len(set(ins[~flags].tolist()) - set(ins[flags].tolist())) > 0                # an item present only as a masked-out input
+        assert len(set(c['sitems'].tolist()) - set(ins.tolist())) > 0                       # an item present only as a negative
+
+
+class StubDevice(object):
+    """Records what the plugin hands to the device; the loss of a step is its number, step `saturate_at` reports saturation."""
+
+    def __init__(self, saturate_at=None):
+        self.calls, self.steps, self.saturate_at = [], [], saturate_at
+
+    def cdae_set_data(self, m, n, ptr, items, counts):
+        self.m, self.n = m, n
+        self.calls.append('cdae_set_data')
+
+    def cdae_set_params(self, U, W, Wd, b, bd):
+        self.p = {'U': U.copy(), 'W': W.copy(), 'Wd': Wd.copy(), 'b': b.copy(), 'bd': bd.copy()}
+        self.calls.append('cdae_set_params')
+
+    def cdae_step(self, users, sptr, sitems, co, seed, lr, reg, step):
+        self.steps.append((list(users), list(sptr), list(sitems), co, seed, lr, reg, step))
+        return (float('inf'), 7) if step == self.saturate_at else (float(step), 0)
+
+    def cdae_get_params(self):
+        self.calls.append('cdae_get_params')
+        return {k: v * 2 for k, v in self.p.items()}
+
+    def cdae_load_factors(self):
+        self.calls.append('cdae_load_factors')
+
+    def set_interactions(self, *a):
+        self.calls.append('set_interactions')
+
+    def get_factors(self):
+        self.calls.append('get_factors')
+        return np.ones((self.m, 4), np.float32), np.ones((self.n, 4), np.float32)
+
+
+def test_plugin_trains_prints_and_loads_factors_on_a_stubbed_device(tmp_path, capsys):
+    z = golden('sampler')
+    rec = _plugin(tmp_path, list(zip(z['ev_u'], z['ev_t'])), [('CDAE=-batch_size 256', 'CDAE=-batch_size %d' % z['batch_size']), ('num.max.iter=100', 'num.max.iter=2')])
+    rec.readConfiguration()
+    np.random.seed(3)
+    rec.initModel()
+    U0 = rec.U.copy()
+    stub = StubDevice()
+    rec.dev = stub
+    random.seed(z['sampler_seed'])
+    capsys.readouterr()
+    rec.buildModel()
+    out = capsys.readouterr().out.splitlines()
+    assert out == ['[1] Epoch: 0001 loss= 1.000000000', '[1] Epoch: 0002 loss= 2.000000000', 'Optimization Finished!']
+    for (users, sets), step in zip(z['batches'], stub.steps):
+        assert step[0] == users and step[2] == [i for s in sets for i in s] and step[1] == np.concatenate([[0], np.cumsum([len(s) for s in sets])]).tolist()
+    assert [s[3:] for s in stub.steps] == [(0.1, 2, 0.6, 0.1, 1), (0.1, 2, 0.6, 0.1, 2)]
+    assert stub.calls == ['cdae_set_data', 'cdae_set_params', 'cdae_get_params', 'cdae_load_factors', 'set_interactions', 'get_factors']
+    assert np.array_equal(rec.U, U0 * 2) and rec.P.shape == (z['m'], 4) and rec._device_factors_current
+
+
+def test_plugin_stops_on_saturation_with_the_loss_line_and_a_message(tmp_path, capsys):
+    z = golden('sampler')
+    rec = _plugin(tmp_path, list(zip(z['ev_u'], z['ev_t'])), [('CDAE=-batch_size 256', 'CDAE=-batch_size 4'), ('num.max.iter=100', 'num.max.iter=5')])
+    rec.readConfiguration()
+    rec.initModel()
+    rec.dev = StubDevice(saturate_at=2)
+    capsys.readouterr()
+    with pytest.raises(SystemExit) as e:
+        rec.buildModel()
+    out = capsys.readouterr().out
+    assert e.value.code == -1 and '[1] Epoch: 0002 loss= inf' in out and 'cdae.hip=-stddev' in out and '7 sampled outputs round to 1.0f' in out
+    assert 'Epoch: 0003' not in out and 'Optimization Finished!' not in out and len(rec.dev.steps) == 2
+
+
+def test_menu_config_and_read_configuration(tmp_path, capsys):
+    from yue_amd.main import MENU
+    from yue_amd.recommender.advanced.CDAE import CDAE
+    from yue_amd.tool.config import Config, LineConfig
+    assert MENU['a4'] == 'CDAE' and callable(CDAE.buildModel)
+    conf = Config(os.path.join(ROOT, 'config', 'CDAE.conf'))
+    opt = LineConfig(conf['CDAE'])
+    assert conf['recommender'] == 'CDAE' and (int(opt['-batch_size']), float(opt['-co']), int(opt['-nh'])) == (256, 0.1, 128)
+    assert float(LineConfig(conf['cdae.hip'])['-stddev']) == 0.25
+    rec = CDAE(conf, [], [])
+    rec.readConfiguration()
+    assert (rec.batch_size, rec.corruption_level, rec.n_hidden, rec.stddev, rec.mask_seed, rec.negative_sp) == (256, 0.1, 128, 0.25, 2, 5)
+    conf.config['CDAE'] = '-batch_size 256 -co 0.1 -nh 64'           # -nh is read and then overwritten (:20, :26)
+    rec = CDAE(conf, [], [])
+    rec.readConfiguration()
+    assert rec.n_hidden == 128
+    conf.config['cdae.hip'] = '-nh 64 -seed 9 -neg 3'                 # this project's override; -stddev back at the reference's 1.0
+    rec = CDAE(conf, [], [])
+    rec.readConfiguration()
+    assert (rec.n_hidden, rec.stddev, rec.mask_seed, rec.negative_sp) == (64, 1.0, 9, 3)
+    for line, said in (('-nh 129', '-nh must be 1 .. 128'), ('-nh 0', '-nh must be 1 .. 128'), ('-stddev 0', '-stddev above 0')):
+        conf.config['cdae.hip'] = line
+        with pytest.raises(SystemExit):
+            CDAE(conf, [], []).readConfiguration()
+        assert said in capsys.readouterr().out, line
+    conf.config['cdae.hip'] = '-stddev 0.25'
+    for line in ('-batch_size 0 -co 0.1 -nh 128', '-batch_size 8 -co 0 -nh 128', '-batch_size 8 -co 1.5 -nh 128'):
+        conf.config['CDAE'] = line
+        with pytest.raises(SystemExit):
+            CDAE(conf, [], []).readConfiguration()
+        assert '-co in (0, 1]' in capsys.readouterr().out, line
+
+
+def test_plugin_refuses_array_native_data(tmp_path, capsys):
+    from yue_amd import synth
+    from yue_amd.data.arrays import ArrayRecord
+    from yue_amd.recommender.advanced.CDAE import CDAE
+    m, n, d = 40, 30, 6
+    data = synth.make_arrays(m, n, d, seed=9)
+    tp, ti = synth.make_test_arrays(m, n, d, 2, data['indptr'], data['indices'], seed=9)
+    rec = CDAE(ce.config(tmp_path, 'one_step'), ArrayRecord(m, n, data['ev_ptr'], data['ev_i'], tp, ti))
+    rec.readConfiguration()
+    capsys.readouterr()
+    with pytest.raises(SystemExit):
+        rec.initModel()
+    assert 'array-native data is not supported' in capsys.readouterr().out
+
+
+@pytest.mark.parametrize('name', ce.TRAINING)
+def test_e2e_logs_keep_the_float32_contract_inside_the_cap(tmp_path, capsys, orc, name):
+    """What tests/test_gpu_cdae_plugin.py asks of the device, asked of the float32 contract: the oracle's lists on its factors equal
+    those on the fp64 factors for every compared user, and at most 2 % of the test users are left out -- also at 4 times the float32
+    contract's distance, the margin the device's other bounds grant over it."""
+    rec, seed = ce.plugin_on_cpu(tmp_path, name)
+    capsys.readouterr()
+    p0 = ce.params(rec)
+    F64, batches, losses = ce.contract_F(rec, p0, seed, np.float64)
+    F32, again, losses32 = ce.contract_F(rec, p0, seed, np.float32)
+    steps = ce.PROBLEMS[name][5]
+    assert batches == again and len(batches) == steps and not any(s for _, s in losses + losses32) and F32.dtype == np.float32
+    assert F64.shape == (rec.m + rec.n, rec.n_hidden + 1) and (F64[:rec.m, -1] == 1).all()
+    assert any(len(set(b[0])) < len(b[0]) for b in batches)          # a user drawn twice in one batch
+    N = max(rec._top_list())
+    names, uids, mp, mi = ce.ranked_users(rec)
+    keep, dist = ce.compared_users(F64, rec.m, uids, mp, mi, N, F32)
+    far = ce.compared_users(F64, rec.m, uids, mp, mi, N, F64 + 4 * (F32.astype(np.float64) - F64))[0]
+    print(name, 'test users', len(uids), 'left out', int((~keep).sum()), 'at 4 x the distance', int((~far).sum()), 'F distance %.3g abs, %.3g rel' % (dist, cd.rel(F32, F64)))
+    assert len(uids) >= 50 and (~keep).sum() <= ce.CAP * len(uids) and (~far).sum() <= ce.CAP * len(uids)
+    want, got = ce.oracle_lists(orc, F64, rec.m, uids, mp, mi, N), ce.oracle_lists(orc, F32, rec.m, uids, mp, mi, N)
+    assert np.array_equal(got[keep], want[keep])
+
+
+def test_e2e_log_as_written_saturates_at_the_first_step(tmp_path, capsys):
+    rec, seed = ce.plugin_on_cpu(tmp_path, 'as_written')
+    capsys.readouterr()
+    assert rec.stddev == 1.0 and rec.n_hidden == 128
+    _, batches, losses = ce.contract_F(rec, ce.params(rec), seed, np.float32)
+    fw = cd.forward(ce.params(rec), rec._user_csr, batches[0][0], *cd.sample_csr([set(s) for s in batches[0][1]]), rec.corruption_level, rec.mask_seed, 1, np.float32)
+    far = int((fw['logit'] > 20).sum())                              # sigmoid rounds to 1.0f from 16.7 on: these are far across
+    print('as_written: float32 contract', losses, 'logits above 20:', far, 'std of the logits %.2f' % fw['logit'].std())
+    assert len(losses) == 1 and losses[0][0] == np.inf and losses[0][1] >= far >= 1

@@ -14,7 +14,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'csrc', 'libyue_hip.so')
 
-OK, ERR_ARG, ERR_HIP, ERR_FEW_ITEMS, ERR_COMM = 0, -1, -2, -3, -4
+OK, ERR_ARG, ERR_HIP, ERR_FEW_ITEMS, ERR_COMM, ERR_SATURATED = 0, -1, -2, -3, -4, -5
 UNIQUE_ID_BYTES = 128
 
 # every symbol include/yue_hip.h declares (checked by tests/test_abi.py)
@@ -34,7 +34,9 @@ SYMBOLS = ['yue_last_error', 'yue_version', 'yue_ctx_create', 'yue_ctx_destroy',
            'yue_cnet_friends',
            'yue_s2v_set_state', 'yue_s2v_get_state', 'yue_s2v_set_steps', 'yue_s2v_set_pairs', 'yue_s2v_epoch',
            'yue_lgcn_set_graph', 'yue_lgcn_propagate', 'yue_lgcn_grad', 'yue_lgcn_step',
-           'yue_ngcf_set_graph', 'yue_ngcf_set_weights', 'yue_ngcf_get_weights', 'yue_ngcf_propagate', 'yue_ngcf_grad', 'yue_ngcf_step']
+           'yue_ngcf_set_graph', 'yue_ngcf_set_weights', 'yue_ngcf_get_weights', 'yue_ngcf_propagate', 'yue_ngcf_grad', 'yue_ngcf_step',
+           'yue_cdae_set_data', 'yue_cdae_set_params', 'yue_cdae_get_params', 'yue_cdae_forward', 'yue_cdae_grad', 'yue_cdae_step',
+           'yue_cdae_load_factors', 'yue_cdae_times']
 
 
 class YueHipError(RuntimeError):
@@ -315,6 +317,93 @@ class Device(object):
         self._chk(self._lib.yue_ngcf_step(self._ctx, C.c_int(layers), C.c_int(int(bool(training))), C.c_double(keep), C.c_uint64(seed), a, b, c,
                                           C.c_int64(len(u)), C.c_double(lr), C.c_double(reg), C.c_int64(step), C.byref(loss)))
         return loss.value
+
+    # -- CDAE (a state of its own: U, W, W', b, b') ----------------------
+    def cdae_set_data(self, m, n, ptr, items, counts):
+        """The user CSR: items ascending and distinct within a user, with their event counts."""
+        ptr, a = _i64(ptr)
+        assert len(ptr) == m + 1 and len(items) == len(counts) and len(items) >= ptr[-1], 'cdae_set_data: ptr [m + 1], one count per item'
+        self.cdae_nnz_ptr = ptr
+        items, b = _i32(items if len(items) else np.zeros(1, np.int32))
+        counts, c = _i32(counts if len(counts) else np.zeros(1, np.int32))
+        self._chk(self._lib.yue_cdae_set_data(self._ctx, C.c_int64(m), C.c_int64(n), a, b, c))
+        self.cdae_m, self.cdae_n = int(m), int(n)
+
+    def cdae_set_params(self, U, W, Wd, b, bd):
+        """U [m, h], encoder W [n, h], decoder Wd [h, n], b [h], bd [n]; the Adam moments are cleared."""
+        arrs = [_f32(x) for x in (U, W, Wd, b, bd)]
+        h = arrs[0][0].shape[1]
+        assert [x[0].shape for x in arrs] == [(self.cdae_m, h), (self.cdae_n, h), (h, self.cdae_n), (h,), (self.cdae_n,)], \
+            'cdae_set_params: U [m, h], W [n, h], Wd [h, n], b [h], bd [n] for the m, n of cdae_set_data'
+        self._chk(self._lib.yue_cdae_set_params(self._ctx, C.c_int(h), *[x[1] for x in arrs]))
+        self.cdae_h = int(h)
+
+    def _cdae_shapes(self):
+        m, n, h = self.cdae_m, self.cdae_n, self.cdae_h
+        return ((m, h), (n, h), (h, n), (h,), (n,))
+
+    def cdae_get_params(self, moments=False):
+        """{'U', 'W', 'Wd', 'b', 'bd'}; with moments also 'mU' .. 'vbd'."""
+        out, sets = {}, []
+        for prefix in ('', 'm', 'v') if moments else ('',):
+            arrs = [np.empty(shape, np.float32) for shape in self._cdae_shapes()]
+            out.update({prefix + key: a for key, a in zip(('U', 'W', 'Wd', 'b', 'bd'), arrs)})
+            sets.append((C.POINTER(C.c_float) * 5)(*[a.ctypes.data_as(C.POINTER(C.c_float)) for a in arrs]))
+        sets += [None] * (3 - len(sets))
+        self._chk(self._lib.yue_cdae_get_params(self._ctx, *sets))
+        return out
+
+    def _cdae_batch(self, users, sptr, sitems):
+        users, a = _i32(users)
+        sptr, b = _i64(sptr)
+        assert len(sptr) == len(users) + 1 and len(sitems) >= sptr[-1], 'cdae: sample_ptr [B + 1] over sample_items'
+        sitems, c = _i32(sitems if len(sitems) else np.zeros(1, np.int32))
+        return (users, sptr, sitems), (a, C.c_int64(len(users)), b, c)
+
+    def cdae_forward(self, users, sptr, sitems, co, seed, step, reg):
+        """(hid [B, h], kept flags per input entry, logits and y_pred per sampled entry, loss)."""
+        keep, args = self._cdae_batch(users, sptr, sitems)
+        B, S = len(keep[0]), int(keep[1][-1])
+        ptr = self.cdae_nnz_ptr
+        q_in = int(sum(ptr[u + 1] - ptr[u] for u in keep[0] if 0 <= u < self.cdae_m))
+        hid = np.empty((B, self.cdae_h), np.float32)
+        kept = np.empty(max(q_in, 1), np.int32)
+        logit, ypred = np.empty(max(S, 1), np.float32), np.empty(max(S, 1), np.float32)
+        loss = C.c_double()
+        self._chk(self._lib.yue_cdae_forward(self._ctx, *args, C.c_double(co), C.c_uint64(seed), C.c_int64(step), C.c_double(reg),
+                                             hid.ctypes.data_as(C.POINTER(C.c_float)), kept.ctypes.data_as(C.POINTER(C.c_int32)),
+                                             logit.ctypes.data_as(C.POINTER(C.c_float)), ypred.ctypes.data_as(C.POINTER(C.c_float)), C.byref(loss)))
+        return hid, kept[:q_in].astype(bool), logit[:S], ypred[:S], loss.value
+
+    def cdae_grad(self, users, sptr, sitems, co, seed, step, reg):
+        """(loss, {'U', 'W', 'Wd', 'b', 'bd'}: the dense gradients); nothing moves."""
+        keep, args = self._cdae_batch(users, sptr, sitems)
+        g = [np.empty(shape, np.float32) for shape in self._cdae_shapes()]
+        loss = C.c_double()
+        self._chk(self._lib.yue_cdae_grad(self._ctx, *args, C.c_double(co), C.c_uint64(seed), C.c_int64(step), C.c_double(reg), C.byref(loss),
+                                          *[x.ctypes.data_as(C.POINTER(C.c_float)) for x in g]))
+        return loss.value, dict(zip(('U', 'W', 'Wd', 'b', 'bd'), g))
+
+    def cdae_step(self, users, sptr, sitems, co, seed, lr, reg, step):
+        """One minibatch step.  Returns (loss, saturated): with saturated > 0 the loss is inf and nothing was updated."""
+        keep, args = self._cdae_batch(users, sptr, sitems)
+        loss = C.c_double()
+        rc = self._lib.yue_cdae_step(self._ctx, *args, C.c_double(co), C.c_uint64(seed), C.c_double(lr), C.c_double(reg), C.c_int64(step), C.byref(loss))
+        if rc == ERR_SATURATED:
+            return loss.value, self.get_option('cdae_last_saturated')
+        self._chk(rc)
+        return loss.value, 0
+
+    def cdae_load_factors(self):
+        """Fills the context's factor matrices on the device with [hid(u) | 1] and [Wd[:, i] | bd[i]] (k = h + 1) for the scan."""
+        self._chk(self._lib.yue_cdae_load_factors(self._ctx))
+        self.m, self.n, self.k = self.cdae_m, self.cdae_n, self.cdae_h + 1
+
+    def cdae_times(self):
+        """Device ns of the last call's (encode, decode, regroup, adam) phases."""
+        ns = (C.c_int64 * 4)()
+        self._chk(self._lib.yue_cdae_times(self._ctx, ns))
+        return tuple(ns)
 
     def default_round_events(self):
         out = C.c_int64()

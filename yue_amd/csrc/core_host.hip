@@ -81,6 +81,7 @@ int yue_ctx_destroy(yue_ctx *c) {
     yue_host::s2v_release(c);
     yue_host::lgcn_release(c);
     yue_host::ngcf_release(c);
+    yue_host::cdae_release(c);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return YUE_OK;

@@ -11,6 +11,7 @@
 //   s2v_host.hip    Song2vec's iteration (level-scheduled rating steps and similarity pairs)
 //   lgcn_host.hip   LightGCN (graph propagation forward and backward, minibatch, Adam step)
 //   ngcf_host.hip   NGCF (weighted graph convolution: gather, MFMA layers forward and backward, weight gradients, Adam step)
+//   cdae_host.hip   CDAE (sparse encoder, sampled decoder, gradients regrouped by item, dense Adam on five variables)
 //   gcn_host.hpp    what those two share (header only): the graph on the device and its hub parts, a product's launches, the
 //                   minibatch, the phase timer
 #pragma once
@@ -36,6 +37,7 @@ struct yue_cnet;                                     // cnet_host.hip: pairs, wa
 struct yue_s2v;                                      // s2v_host.hip: biases, steps, pairs and their level schedules of Song2vec's iteration
 struct yue_lgcn;                                     // lgcn_host.hip: the graph (gcn_host.hpp), layers and gradients of LightGCN
 struct yue_ngcf;                                     // ngcf_host.hip: the graph and its transpose (gcn_host.hpp), weights, layers and gradients of NGCF
+struct yue_cdae;                                     // cdae_host.hip: user CSR, the five variables with their moments, the batch's index arrays of CDAE
 struct yue_ipf;                                      // ipf_host.hip: session temporal graph, weights, per-slot work arrays of IPF
 
 namespace yue_host {
@@ -229,6 +231,11 @@ struct yue_ctx {
     int64_t opt_ngcf_hub = 1024;         // NGCF: as lgcn_hub, for the graph and its transpose
     int64_t ngcf_hubs = 0, ngcf_parts = 0;   // ... hub rows and parts of both matrices in the last call (read-only options ngcf_last_hubs / ngcf_last_parts)
     int64_t ngcf_ns[6] = {0, 0, 0, 0, 0, 0};   // device time of the last call's gather, dense, batch, backward, wgrad and adam phases (read-only options ngcf_last_*_ns)
+    yue_cdae *cdae = nullptr;            // CDAE state (yue_cdae_*), owned by cdae_host.hip
+    int64_t opt_cdae_hub = 1024;         // CDAE: encoder rows and regrouped segments with more entries are cut into parts of this many (the default is lgcn_hub's, unmeasured here)
+    int64_t cdae_hubs = 0, cdae_parts = 0;   // ... such rows / segments and their parts in the last call (read-only options cdae_last_hubs / cdae_last_parts)
+    int64_t cdae_saturated = 0;          // sampled outputs with y_pred == 1.0f in the last call (read-only option cdae_last_saturated)
+    int64_t cdae_ns[4] = {0, 0, 0, 0};   // device time of the last call's encode, decode, regroup and adam phases (yue_cdae_times)
 };
 
 namespace yue_host {
@@ -292,4 +299,6 @@ int s2v_get_option(yue_ctx *c, const std::string &key, int64_t *value);
 void lgcn_release(yue_ctx *c);
 // ngcf_host.hip: frees the NGCF state (its options are rows of the option table)
 void ngcf_release(yue_ctx *c);
+// cdae_host.hip: frees the CDAE state (its options are rows of the option table)
+void cdae_release(yue_ctx *c);
 }  // namespace yue_host

@@ -134,6 +134,11 @@ const Option kOptions[] = {
     {"ngcf_last_backward_ns", YUE_AT(ngcf_ns[3])},
     {"ngcf_last_wgrad_ns", YUE_AT(ngcf_ns[4])},
     {"ngcf_last_adam_ns", YUE_AT(ngcf_ns[5])},
+    // CDAE (cdae_host.hip)
+    {"cdae_hub", YUE_AT(opt_cdae_hub), set_ranged, 1, 0x7fffffff, "must be 1 .. 2^31 - 1"},
+    {"cdae_last_hubs", YUE_AT(cdae_hubs)},
+    {"cdae_last_parts", YUE_AT(cdae_parts)},
+    {"cdae_last_saturated", YUE_AT(cdae_saturated)},
 };
 #undef YUE_AT
 
