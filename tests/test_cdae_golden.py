@@ -168,6 +168,113 @@ def test_every_gpu_case_reaches_its_branch_and_meets_its_conditioning_statement(
         assert len(set(c['sitems'].tolist()) - set(ins.tolist())) > 0                       # an item present only as a negative
 
 
+@pytest.mark.parametrize('name', cc.EDGE_NAMES)
+def test_every_edge_case_reaches_its_edge_and_meets_the_conditioning_statement(name):
+    """The cases of tests/test_gpu_cdae_edges.py.  Nothing a device computes enters here: the conditioning is the fp64 and float32
+    contracts', the edges are read off the case's data and batch."""
+    c = cc.build(name)
+    lay, fw, users, sets, n, h = c['layout'], c['fw'], c['users'], c['sets'], c['n'], c['h']
+    ptr, items, cnt = c['data']
+    hub = c['hub'] if c['hub'] else 1024
+    deg = [int(ptr[u + 1] - ptr[u]) for u in users]
+    sizes = np.diff(c['sptr']).tolist()
+    S = int(c['sptr'][-1])
+    flags = np.concatenate(fw['flags']) if sum(deg) else np.zeros(0, bool)
+    fam, lens = cc.families(c), cc.family_lengths(c)
+    print(name, 'max |logit| %.3g' % c['logit_max'], 'hid %.3g .. %.3g' % (fw['hid'].min(), fw['hid'].max()), 'hubs, parts', cc.hubs_and_parts(c, hub),
+          ' '.join('%s %.3g' % kv for kv in sorted(c['d32'].items())))
+    # the conditioning statement of every case
+    assert c['logit_max'] <= 10 and max(c['d32'].values()) <= 1e-6 and c['saturated'] == 0
+    assert set(c['d32']) == set(cc.QUANTITIES) and set(c['L']) == set(cc.QUANTITIES)
+    # what every edge case sets instead of drawing: degrees, batch users, exact sample sizes; the sets as the builder describes them
+    assert np.diff(ptr).tolist() == lay['deg'] and users == lay['users'] and sizes == lay['sizes'] == [len(s) for s in sets] and len(users) == c['B']
+    assert cnt.min() == 1 and cnt.max() == 3
+    for s, u in enumerate(users):
+        mine = items[ptr[u]:ptr[u + 1]].tolist()
+        assert set(mine[:sizes[s]]) <= sets[s] and (sizes[s] >= len(mine) or sets[s] == set(mine[:sizes[s]]))
+    # the host's count of hubs and parts is the one made from the family lengths with Python sets
+    assert cd.hub_counts(c['data'], users, c['sptr'], c['sitems'], hub) == cc.hubs_and_parts(c, hub)
+    kind = c['kind']
+    if kind == 'enc':
+        assert n == 200 and h == 20 and c['co'] == 0.5 and c['w_std'] == cc.W_STD_LONG < cc.STDDEV
+        assert tuple(deg[:7]) == cc.CHUNK_LENGTHS == (0, 1, 63, 64, 65, 128, 129) and all(1 <= d <= 8 for d in deg[7:]) and len(deg) > 7
+        assert lens['users'] == [1] * len(users) and lay['score_users'] == users[:7]
+        assert cc.HID_RANGE[0] <= fw['hid'].min() and fw['hid'].max() <= cc.HID_RANGE[1]                    # no slot's dz is blinded
+        for s in range(2, 7):                                        # a kept and a dropped entry in every chunk of every long row
+            for base in range(0, deg[s], 64):
+                part = fw['flags'][s][base:base + 64]
+                assert part.any() and (len(part) == 1 or not part.all()), (s, base)
+        assert cc.build('enc_chunks')['data'][1].tobytes() == cc.build('enc_chunks_hub96')['data'][1].tobytes()   # the same data
+        if c['hub'] is None:
+            assert cc.hubs_and_parts(c, hub) == (0, 0)
+        else:                                                        # 128 = 96 + 32, 129 = 96 + 33: the first part spans two chunks
+            assert c['hub'] == 96 and cc.hubs_and_parts(c, hub) == (2, 4) and max(lens['sampled'] + lens['inputs'] + lens['batch']) <= 96
+    if kind == 'dec':
+        assert tuple(sizes) == cc.CHUNK_LENGTHS and n >= 129 and all(1 <= d <= 8 for d in deg) and lens['users'] == [1] * 7
+        assert h == (65 if name == 'dec_chunks_h65' else 20)
+        assert deg[0] > 0 and fw['flags'][0].any() and not fw['dz'][0].any()    # the empty sample: kept inputs, but nothing reaches dz
+        assert np.array_equal(c['g']['U'][users[0]], cc.REG * c['p']['U'][users[0]].astype(np.float64))
+        assert fw['y_true'].max() > 1                                # a kept count above 1 among the sampled entries
+    if kind == 'nothing':
+        assert c['B'] == 2 and users == [0, 0] and deg == [0, 0] and S == 0 and sum(deg) == 0 and len(fam['sampled']) == len(fam['inputs']) == 0
+        p64 = {k: v.astype(np.float64) for k, v in c['p'].items()}
+        l2 = sum((p64[k] ** 2).sum() / 2 for k in ('W', 'Wd', 'b', 'bd')) + 2 * (p64['U'][0] ** 2).sum() / 2
+        assert abs(c['loss'] - (cd.UNSAMPLED + cc.REG * l2)) <= 1e-14 * c['loss']             # the unsampled constant and the reg term
+        for k in ('W', 'Wd', 'b', 'bd'):
+            assert np.array_equal(c['g'][k], cc.REG * p64[k]), k
+        want = np.zeros_like(p64['U'])
+        want[0] = 2 * (cc.REG * p64['U'][0])                        # reg U[u] once per slot
+        assert np.array_equal(c['g']['U'], want)
+    if kind == 'small':
+        assert (c['m'], n, c['B']) == (40, 70, 16) and deg[:3] == [0, 40, 1] and users[3] == users[4]
+        if name.startswith('h') and name != 'hub1':
+            assert name == 'h%d' % h and h in (1, 63, 65, 127) and c['hub'] is None and c['co'] == 0.5
+        if name == 'hub1':
+            assert c['hub'] == 1 and h == 20
+            hubs, parts = cc.hubs_and_parts(c, 1)                    # every segment of two or more entries is a hub, an entry is a part
+            every = [x for v in lens.values() for x in v]
+            assert hubs == sum(1 for x in every if x >= 2) and parts == sum(x for x in every if x >= 2) and hubs >= 50
+        if name == 'all_dropped':
+            assert c['co'] == 1e-9 and cd.threshold(c['co']) == 0 and len(flags) == sum(deg) > 0 and not flags.any() and not fw['y_true'].any()
+            assert np.array_equal(c['g']['W'], cc.REG * c['p']['W'].astype(np.float64))
+            b64, U64 = c['p']['b'].astype(np.float64), c['p']['U'].astype(np.float64)
+            assert np.array_equal(fw['hid'], 1 / (1 + np.exp(-(b64[None, :] + U64[users]))))
+        else:
+            assert flags.any() and not flags.all()
+    if kind in ('parts', 'parts_b', 'parts_rows'):
+        assert c['hub'] == cc.PARTS_HUB == 4 and cc.PART_LENGTHS == (3, 4, 5, 8, 9)
+        # the three batches together: each of the five families holds hub - 1, hub, hub + 1, 2 hub and 2 hub + 1 (the whole batch
+        # is one segment per batch: 2 hub + 1 twice and 4 hub + 1)
+        three = [cc.family_lengths(cc.build(k)) for k in ('parts', 'parts_b', 'parts_rows')]
+        for family in ('rows', 'sampled', 'inputs', 'users'):
+            assert set(cc.PART_LENGTHS) <= set(x for one in three for x in one[family]), family
+        assert [one['batch'] for one in three] == [[9], [17], [9]]
+    if kind == 'parts':                                              # slots by user: 5 and 4; sampled entries by item: all five lengths
+        assert c['B'] == 2 * hub + 1 and lens['users'] == [4, 5] and sorted(set(deg)) == [5, 8]
+        assert all(fam['sampled'][i] == k and i not in fam['inputs'] for i, k in lay['sampled_by'].items()) and sorted(lay['sampled_by'].values()) == [3, 4, 5, 8, 9]
+        assert fam['inputs'][10] == 9 and {4, 5, 9} <= set(lens['inputs'])
+    if kind == 'parts_b':                                            # slots by user: 8 and 9
+        assert c['B'] == 4 * hub + 1 and lens['users'] == [8, 9] and fam['inputs'][10] == 17 and fam['sampled'][10] == 17
+    if kind == 'parts_rows':                                         # encoder rows, input entries by item, sampled entries by item
+        assert c['B'] == 2 * hub + 1 and sorted(set(deg)) == [3, 4, 5, 8, 9] and lens['users'] == [1, 1, 2, 2, 3]
+        assert all(fam['inputs'][i] == k and fam['sampled'][i] == k for i, k in lay['held_by'].items()) and sorted(lay['held_by'].values()) == [3, 4, 5, 8, 9]
+    if kind in ('parts', 'parts_b', 'parts_rows'):
+        assert flags.any() and not flags.all()
+    if kind == 'stride':
+        first = cc.GRID // h                                         # the first item row of the loop's second trip
+        assert cc.GRID == 8192 * 256 and n * h == cc.GRID + 2048 > cc.GRID and first == 16384 and n - first == 16 and c['m'] == 40 and c['B'] == 8
+        assert c['m'] * h <= cc.GRID                                 # (U and the vectors stay inside the first trip)
+        held = set(fam['inputs'])
+        kept_in = set(int(i) for s, u in enumerate(users) for i in items[ptr[u]:ptr[u + 1]][fw['flags'][s]])
+        only_sampled = set(fam['sampled']) - held
+        outside = set(range(n)) - set(fam['sampled']) - held
+        for side, rows in (('first trip', range(0, first)), ('second trip', range(first, n))):
+            rows = set(rows)
+            assert only_sampled & rows and kept_in & rows and outside & rows, side
+        assert (held - kept_in) & set(range(first, n))              # and a dropped input in the second trip
+        assert all(int(i) < first for u in range(c['m']) if u != 9 for i in items[ptr[u]:ptr[u + 1]])
+
+
 class StubDevice(object):
     """Records what the plugin hands to the device; the loss of a step is its number, step `saturate_at` reports saturation."""
 

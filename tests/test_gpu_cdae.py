@@ -37,26 +37,34 @@ def batch(c):
 def check_forward(dev, c):
     fw = c['fw']
     hid, kept, logit, ypred, loss = dev.cdae_forward(*batch(c))
-    got = {'hid': cd.rel(hid, fw['hid']), 'logit': cd.rel(logit, fw['logit']), 'y_pred': cd.rel(ypred, fw['y_pred'])}
+    got = {'hid': cc.rel(hid, fw['hid']), 'logit': cc.rel(logit, fw['logit']), 'y_pred': cc.rel(ypred, fw['y_pred'])}
     assert np.array_equal(kept, np.concatenate(fw['flags']) if len(kept) else np.zeros(0, bool)), 'kept flags'
     return got, loss, (hid, kept, logit, ypred)
 
 
-@pytest.mark.parametrize('name', [n for n in cc.GPU_CASES if n != 'sat'])
-def test_forward_mask_loss_and_gradients(dev, name):
-    c = cc.build(name)
-    upload(dev, c)
-    got, loss, _ = check_forward(dev, c)
+def check_gradients(dev, c, hub=None):
+    """Uploads the case (at `hub`, else at its own cdae_hub) and holds forward, loss and the five gradients to the case's bounds,
+    the kept flags and the hub and part counts to the host's.  Returns (the gradients, every output in a fixed order)."""
+    upload(dev, c, hub)
+    got, loss, out = check_forward(dev, c)
     loss_g, g = dev.cdae_grad(*batch(c))
     assert loss_g == loss and dev.get_option('cdae_last_saturated') == 0
     got['loss'] = abs(loss - c['loss']) / abs(c['loss'])
     for k in cd.NAMES:
         got[k] = cd.rel(g[k], c['g'][k])
-    print(name, ' '.join('%s %.3g (d32 %.3g, x%.2f)' % (k, got[k], c['d32'][k], got[k] / c['d32'][k] if c['d32'][k] else 0.0) for k in cc.QUANTITIES))
+    print(c['name'], ' '.join('%s %.3g (d32 %.3g, x%.2f)' % (k, got[k], c['d32'][k], got[k] / c['d32'][k] if c['d32'][k] else 0.0) for k in cc.QUANTITIES))
     for k in cc.QUANTITIES:
         assert got[k] <= cc.bound(c, k), (k, got[k], c['d32'][k], cc.bound(c, k))
-    hubs, parts = cd.hub_counts(c['data'], c['users'], c['sptr'], c['sitems'], c['hub'] if c['hub'] else 1024)
+    hubs, parts = cd.hub_counts(c['data'], c['users'], c['sptr'], c['sitems'], hub if hub else (c['hub'] if c['hub'] else 1024))
     assert dev.get_option('cdae_last_hubs') == hubs and dev.get_option('cdae_last_parts') == parts
+    return g, list(out) + [np.float64(loss)] + [g[k] for k in cd.NAMES]
+
+
+@pytest.mark.parametrize('name', [n for n in cc.GPU_CASES if n != 'sat'])
+def test_forward_mask_loss_and_gradients(dev, name):
+    c = cc.build(name)
+    g, _ = check_gradients(dev, c)
+    hubs, parts = cd.hub_counts(c['data'], c['users'], c['sptr'], c['sitems'], c['hub'] if c['hub'] else 1024)
     if c['special'] == 'hub':
         assert hubs >= 3 and parts >= 9                          # the user of 40 items, the item of every slot, the batch itself
     if c['special'] == 'low':                                    # the clamped column passes no gradient: its rows hold the decay alone
@@ -83,15 +91,16 @@ def test_saturated_outputs_are_counted_the_loss_is_inf_and_a_step_moves_nothing(
         assert k in cd.NAMES or not after[k].any()               # the moments: still zero
 
 
-@pytest.mark.parametrize('name', ['h2', 'h33', 'twice', 'keep01'])
-def test_step_is_the_contracts_adam_on_the_devices_gradients(dev, name):
-    c = cc.build(name)
-    lr = 0.002
+def check_steps(dev, c, lr=0.002, steps=(1, 2, 3), after=None):
+    """yue_cdae_step against the contract's float32 Adam fed the device's own gradients, over whole arrays.  after(t, loss, g, before,
+    got) sees each step's loss and gradients and the parameters and moments around it."""
+    name = c['name']
     upload(dev, c)
     p = {k: v.copy() for k, v in c['p'].items()}
     st = cd.new_state(p)
     users, sptr, sitems, co, seed, _, reg = batch(c)
-    for t in (1, 2, 3):
+    for t in steps:
+        before = {k: v.copy() for k, v in list(p.items()) + list(st.items())}
         loss_g, g = dev.cdae_grad(users, sptr, sitems, co, seed, t, reg)
         loss, sat = dev.cdae_step(users, sptr, sitems, co, seed, lr, reg, t)
         assert loss == loss_g and sat == 0
@@ -107,12 +116,19 @@ def test_step_is_the_contracts_adam_on_the_devices_gradients(dev, name):
         if t == 2:
             outside = np.setdiff1d(np.arange(c['m']), users)
             assert len(outside) and (got['vU'][outside] == 0).all() and (got['U'][outside] == c['p']['U'][outside]).all()
+        if after:
+            after(t, loss, g, before, got)
         # the contract goes on from the device's state, so that a step's check does not inherit the last one's rounding
         for k in cd.NAMES:
             p[k] = got[k].copy()
         for k in st:
             st[k] = got[k].copy()
     assert all(t > 0 for t in dev.cdae_times())
+
+
+@pytest.mark.parametrize('name', ['h2', 'h33', 'twice', 'keep01'])
+def test_step_is_the_contracts_adam_on_the_devices_gradients(dev, name):
+    check_steps(dev, cc.build(name))
 
 
 @pytest.mark.parametrize('name', ['h64', 'hub'])
@@ -131,9 +147,9 @@ def test_repeat_runs_are_bit_identical(dev, name):
         assert np.array_equal(a, b)
 
 
-@pytest.mark.parametrize('name', ['h128', 'h33', 'hub'])
-def test_load_factors_then_scores_are_the_contracts_logits(dev, name):
-    c = cc.build(name)
+def check_factors(dev, c, users):
+    """yue_cdae_load_factors against the contract's factors, then the scores of `users` against its logits."""
+    name = c['name']
     upload(dev, c)
     dev.cdae_load_factors()
     p64 = {k: v.astype(np.float64) for k, v in c['p'].items()}
@@ -147,10 +163,16 @@ def test_load_factors_then_scores_are_the_contracts_logits(dev, name):
     longest = int(np.diff(c['data'][0]).max())
     bound = max(4 * d32, max(longest + 2, c['h'] + 1) * 2.0 ** -24)
     worst = 0.0
-    for u in (0, 1, 2, c['m'] - 1):                              # no items, 40 items (parts at hub 8), one item, the last user
+    for u in users:
         worst = max(worst, float(np.abs(dev.scores(u) - want[u]).max() / np.abs(want).max()))
     print(name, 'scores %.3g (d32 %.3g, bound %.3g)' % (worst, d32, bound), 'hid', cd.rel(P[:, :-1], P64[:, :-1]))
     assert worst <= bound and cd.rel(P, P64) <= max(4 * cd.rel(P32, P64), (longest + 2) * 2.0 ** -24)
+
+
+@pytest.mark.parametrize('name', ['h128', 'h33', 'hub'])
+def test_load_factors_then_scores_are_the_contracts_logits(dev, name):
+    c = cc.build(name)
+    check_factors(dev, c, (0, 1, 2, c['m'] - 1))                 # no items, 40 items (parts at hub 8), one item, the last user
 
 
 def test_refusals(dev):
