@@ -250,7 +250,14 @@ int yue_get_option(yue_ctx *ctx, const char *name, int64_t *value);
  *                    rounds of round_users consecutive users; every user of a round runs the reference's whole per-user
  *                    loop on the model as it was when the round started plus its own changes, the per-row differences of
  *                    the round's users are summed and added once.  round_users = 1 is yue_fism_epoch.  Same arguments
- *                    and outputs otherwise.
+ *                    and outputs otherwise.  Read-only option "fism_last_form": the form the last call took -- 0 k_fism_round
+ *                    (working rows in global memory), 1 k_fism_round_lds<KR, false>, 2 k_fism_round_lds<KR, true> (round-start
+ *                    rows in LDS beside the working rows).
+ *   Negatives (both calls): a draw whose negative equals its OWN event's item is refused with YUE_ERR_ARG (the message names
+ *                    the draw) before anything is uploaded or changed: the reference rejects the user's items when it draws
+ *                    (FISM.py:50-53) and cannot produce it, and the device forms would not follow the reference's sequential
+ *                    update for it (Bi[i], then Bi[j] from the updated value; likewise Q).  A negative equal to ANOTHER item
+ *                    of the same user is accepted and shares that item's row, as in the reference's arithmetic.
  *   yue_fism_scores  replaces FISM.predict (FISM.py:75-83) for a user whose training events are `items`.
  *   yue_fism_topn_scan  predict + the selection of base/IterativeRecommender.py:98-145 for nu users given as a
  *                    CSR of their training events (mask = those items).  YUE_ERR_FEW_ITEMS as yue_topn_scan.

@@ -31,7 +31,7 @@ RANGES = {
 
 # name -> value on a fresh context (round_path: no factors yet, the epoch path's metadata form is the default)
 READ_ONLY = {'scan_last_chunks': 0, 'scan_last_few_users': 0, 'scan_last_settle': 0, 'round_last_stage_max': 0, 'comm_last_compute_waits': 0,
-             'round_last_user_seq': 0, 'chain_last_us': 0, 'chain_last_runs': 0, 'chain_last_waves': 0, 'replay_last_levels': 0, 'round_path': 1}
+             'round_last_user_seq': 0, 'fism_last_form': 0, 'chain_last_us': 0, 'chain_last_runs': 0, 'chain_last_waves': 0, 'replay_last_levels': 0, 'round_path': 1}
 
 # options with a setter of their own
 OTHER = {'round_cus_reserved': 0, 'round_tpw': 0}
@@ -59,7 +59,7 @@ def test_every_option_reads_its_default_on_a_fresh_context(dev):
     want.update({name: row[0] for name, row in RANGES.items()})
     want.update(READ_ONLY)
     want.update(OTHER)
-    assert len(want) == len(FLAGS) + len(RANGES) + len(READ_ONLY) + len(OTHER) == 39
+    assert len(want) == len(FLAGS) + len(RANGES) + len(READ_ONLY) + len(OTHER) == 40
     for name, value in want.items():
         assert dev.get_option(name) == value, name
 

@@ -110,6 +110,7 @@ class Device(object):
         self._raise = raise_errors
         self._ctx = C.c_void_p()
         self.m = self.n = self.k = self.E = 0
+        self.fn = self.fk = 0
         self.knn_m = self.knn_n = 0
         self.ipf_m = self.ipf_n = 0
         self.cnet_m = self.cnet_dim = 0
@@ -487,8 +488,8 @@ class Device(object):
         Q, b = _f32(Q)
         Bi, c = _f64(Bi)
         assert P.shape == Q.shape and len(Bi) == P.shape[0]
-        self.fn, self.fk = P.shape
-        self._chk(self._lib.yue_fism_set_model(self._ctx, a, b, c, C.c_int64(self.fn), C.c_int(self.fk)))
+        self._chk(self._lib.yue_fism_set_model(self._ctx, a, b, c, C.c_int64(P.shape[0]), C.c_int(P.shape[1])))
+        self.fn, self.fk = P.shape                       # (after the check: a refused upload leaves the earlier model and its shape)
 
     def fism_get_model(self, P, Q, Bi):
         """Copies the device model into the given arrays (float64 [n,k], float32 [n,k], float64 [n])."""
@@ -524,9 +525,10 @@ class Device(object):
         return half.value, sums[0], sums[1], sums[2]
 
     def fism_scores(self, items):
-        items, a = _i32(items if len(items) else np.zeros(1, np.int32))
+        n_items = len(items)                             # (an empty row is passed as a placeholder of one element and a length of 0)
+        items, a = _i32(items if n_items else np.zeros(1, np.int32))
         out = np.empty(self.fn, np.float64)
-        self._chk(self._lib.yue_fism_scores(self._ctx, a, C.c_int64(len(items)), out.ctypes.data_as(C.POINTER(C.c_double))))
+        self._chk(self._lib.yue_fism_scores(self._ctx, a, C.c_int64(n_items), out.ctypes.data_as(C.POINTER(C.c_double))))
         return out
 
     def fism_topn_scan(self, row_ptr, row_items, N):

@@ -36,16 +36,56 @@ int yue_fism_get_model(yue_ctx *c, double *P, float *Q, double *Bi) {
 }
 
 namespace {
-// uploads a CSR of item rows (user_ptr[rows+1], items) after checking it
-int fism_upload_rows(yue_ctx *c, const int64_t *ptr, int64_t rows, const int32_t *items, const char *who) {
+// checks a CSR of item rows (user_ptr[rows+1], items) against the uploaded model
+int fism_check_rows(yue_ctx *c, const int64_t *ptr, int64_t rows, const int32_t *items, const char *who) {
     if (rows < 0 || !ptr || ptr[0] != 0) return fail(YUE_ERR_ARG, std::string(who) + ": bad row pointer");
     for (int64_t r = 0; r < rows; ++r) if (ptr[r + 1] < ptr[r]) return fail(YUE_ERR_ARG, std::string(who) + ": row pointer must be non-decreasing");
     const int64_t E = ptr[rows];
     if (E > 0 && !items) return fail(YUE_ERR_ARG, std::string(who) + ": null items");
     for (int64_t e = 0; e < E; ++e) if (items[e] < 0 || items[e] >= c->fn) return fail(YUE_ERR_ARG, std::string(who) + ": item id out of range");
+    return YUE_OK;
+}
+// ... and uploads it (checked: fism_check_rows has passed already)
+int fism_upload_rows(yue_ctx *c, const int64_t *ptr, int64_t rows, const int32_t *items, const char *who, bool checked = false) {
+    if (!checked) { const int rc = fism_check_rows(c, ptr, rows, items, who); if (rc) return rc; }
+    const int64_t E = ptr[rows];
     HIPCHK(c->f_ptr.resize((size_t)rows + 1)); HIPCHK(c->f_items.resize((size_t)std::max<int64_t>(E, 1)));
     HIPCHK(hipMemcpyAsync(c->f_ptr.p, ptr, ((size_t)rows + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
     if (E > 0) HIPCHK(hipMemcpyAsync(c->f_items.p, items, (size_t)E * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    return YUE_OK;
+}
+// The draws of a pass, one linear walk (rows checked already): rho per event of every user with more than one event, every
+// negative a valid item, and none equal to its OWN event's item -- the reference rejects a user's items when it draws
+// (FISM.py:50-53), so it never produces that draw, and for it the device forms would not follow the reference's sequential
+// update (Bi[i], then Bi[j] from the updated value: the device keeps the negative's values).  A negative equal to ANOTHER item
+// of the user passes: it shares that item's row.  Nothing has been uploaded or changed when this refuses.
+int fism_check_draws(yue_ctx *c, const int64_t *user_ptr, int64_t m, const int32_t *ev_i, const int32_t *negs, int64_t n_negs, int rho, const char *who) {
+    int64_t need = 0;
+    for (int64_t u = 0; u < m; ++u) { const int64_t nu = user_ptr[u + 1] - user_ptr[u]; if (nu > 1) need += nu * rho; }
+    if (need != n_negs) return fail(YUE_ERR_ARG, std::string(who) + ": need rho negatives per event of every user with more than one event (" + std::to_string(need) + "), got " + std::to_string(n_negs));
+    // first without a branch per draw (this pass lies in every call's time), then, only if something is wrong, again to say what
+    const uint32_t n32 = (uint32_t)c->fn;
+    unsigned bad = 0;
+    int64_t t = 0;
+    for (int64_t u = 0; u < m; ++u) {
+        if (user_ptr[u + 1] - user_ptr[u] <= 1) continue;
+        for (int64_t e = user_ptr[u]; e < user_ptr[u + 1]; ++e) {
+            const int32_t i = ev_i[e];
+            for (int d = 0; d < rho; ++d, ++t) bad |= (unsigned)((uint32_t)negs[t] >= n32) | (unsigned)(negs[t] == i);
+        }
+    }
+    if (!bad) return YUE_OK;
+    t = 0;
+    for (int64_t u = 0; u < m; ++u) {
+        if (user_ptr[u + 1] - user_ptr[u] <= 1) continue;
+        for (int64_t e = user_ptr[u]; e < user_ptr[u + 1]; ++e) {
+            const int32_t i = ev_i[e];
+            for (int d = 0; d < rho; ++d, ++t) {
+                if (negs[t] < 0 || negs[t] >= c->fn) return fail(YUE_ERR_ARG, std::string(who) + ": negative item id out of range");
+                if (negs[t] == i) return fail(YUE_ERR_ARG, std::string(who) + ": draw " + std::to_string(t) + " (event " + std::to_string(e) + ", user " + std::to_string(u) + ") names its own event's item " + std::to_string(i) + " as its negative");
+            }
+        }
+    }
     return YUE_OK;
 }
 }  // namespace
@@ -55,12 +95,11 @@ int yue_fism_epoch(yue_ctx *c, const int64_t *user_ptr, int64_t m, const int32_t
     if (!c || c->fn == 0) return fail(YUE_ERR_ARG, "yue_fism_epoch: no FISM model uploaded");
     if (m <= 0 || rho < 1 || !coef || (n_negs > 0 && !negs)) return fail(YUE_ERR_ARG, "yue_fism_epoch: bad argument");
     HIPCHK(hipSetDevice(c->device));
-    int rc = fism_upload_rows(c, user_ptr, m, ev_i, "yue_fism_epoch");
-    if (rc) return rc;
-    int64_t need = 0, widest = 1;
-    for (int64_t u = 0; u < m; ++u) { const int64_t nu = user_ptr[u + 1] - user_ptr[u]; if (nu > 1) need += nu * rho; widest = std::max(widest, nu); }
-    if (need != n_negs) return fail(YUE_ERR_ARG, "yue_fism_epoch: need rho negatives per event of every user with more than one event (" + std::to_string(need) + "), got " + std::to_string(n_negs));
-    for (int64_t t = 0; t < n_negs; ++t) if (negs[t] < 0 || negs[t] >= c->fn) return fail(YUE_ERR_ARG, "yue_fism_epoch: negative item id out of range");
+    int rc = fism_check_rows(c, user_ptr, m, ev_i, "yue_fism_epoch");
+    if (rc || (rc = fism_check_draws(c, user_ptr, m, ev_i, negs, n_negs, rho, "yue_fism_epoch"))) return rc;
+    if ((rc = fism_upload_rows(c, user_ptr, m, ev_i, "yue_fism_epoch", true))) return rc;
+    int64_t widest = 1;
+    for (int64_t u = 0; u < m; ++u) widest = std::max(widest, user_ptr[u + 1] - user_ptr[u]);
     HIPCHK(c->f_negs.resize((size_t)std::max<int64_t>(n_negs, 1))); HIPCHK(c->f_coef.resize((size_t)m)); HIPCHK(c->f_x.resize((size_t)widest * c->fk));
     if (n_negs > 0) HIPCHK(hipMemcpyAsync(c->f_negs.p, negs, (size_t)n_negs * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->f_coef.p, coef, (size_t)m * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -86,14 +125,14 @@ int yue_fism_rounds(yue_ctx *c, const int64_t *user_ptr, int64_t m, const int32_
     if (!c || c->fn == 0) return fail(YUE_ERR_ARG, "yue_fism_rounds: no FISM model uploaded");
     if (m <= 0 || rho < 1 || round_users < 1 || !coef || (n_negs > 0 && !negs)) return fail(YUE_ERR_ARG, "yue_fism_rounds: bad argument");
     HIPCHK(hipSetDevice(c->device));
-    int rc = fism_upload_rows(c, user_ptr, m, ev_i, "yue_fism_rounds");
-    if (rc) return rc;
+    int rc = fism_check_rows(c, user_ptr, m, ev_i, "yue_fism_rounds");
+    if (rc || (rc = fism_check_draws(c, user_ptr, m, ev_i, negs, n_negs, rho, "yue_fism_rounds"))) return rc;
+    if ((rc = fism_upload_rows(c, user_ptr, m, ev_i, "yue_fism_rounds", true))) return rc;
     const int64_t E = user_ptr[m];
     // per user: first draw, the sorted unique list of the items it touches, and every event's / draw's position in it
     std::vector<int64_t> neg_ptr((size_t)m + 1, 0), uq_ptr((size_t)m + 1, 0);
     for (int64_t u = 0; u < m; ++u) { const int64_t nu = user_ptr[u + 1] - user_ptr[u]; neg_ptr[(size_t)u + 1] = neg_ptr[(size_t)u] + (nu > 1 ? nu * rho : 0); }
-    if (neg_ptr[(size_t)m] != n_negs) return fail(YUE_ERR_ARG, "yue_fism_rounds: need rho negatives per event of every user with more than one event (" + std::to_string(neg_ptr[(size_t)m]) + "), got " + std::to_string(n_negs));
-    for (int64_t t = 0; t < n_negs; ++t) if (negs[t] < 0 || negs[t] >= c->fn) return fail(YUE_ERR_ARG, "yue_fism_rounds: negative item id out of range");
+    c->fism_form = 0;
     {
         // Fast form (round 3): every user touches at most 64 rows and they fit in LDS -> k_fism_round_lds finds the rows itself;
         // the host prepares nothing per user (the sorted item lists below took most of the call's time).
@@ -142,6 +181,7 @@ int yue_fism_rounds(yue_ctx *c, const int64_t *user_ptr, int64_t m, const int32_
             HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
             const bool start = 2 * lds_rows <= 160u * 1024u && std::min(m, round_users) <= (int64_t)cus * (int64_t)((160u * 1024u) / (2 * lds_rows));
             const size_t lds_launch = start ? 2 * lds_rows : lds;
+            c->fism_form = start ? 2 : 1;
             const void *kfn = with_kr(c->fk, [&](auto kr) {
                 return start ? (const void *)yue::k_fism_round_lds<kr(), true> : (const void *)yue::k_fism_round_lds<kr(), false>;
             });

@@ -485,8 +485,10 @@ __global__ void __launch_bounds__(64) k_fism_round_lds(FismArgs a, FismLdsArgs r
                 if (el < k) wq[j * k + el] = nj[r];
             }
             bi = bin;
-            if (j == i) {                                               // (the reference never draws one of the user's own items; as the
-                bi = bjn;                                               // earlier forms: the negative's values are the ones that stay)
+            if (j == i) {                                               // (unreachable through the C ABI: fism_host.hip refuses a negative equal
+                bi = bjn;                                               // to its own event's item.  Kept as the earlier forms' store order has
+                                                                        // it: the negative's values are the ones that stay -- which is NOT the
+                                                                        // reference's sequential update of Bi[i], then Bi[j] from the new value)
 #pragma unroll
                 for (int r = 0; r < KR; ++r) qi[r] = nj[r];
             }

@@ -180,6 +180,7 @@ struct yue_ctx {
     int fk = 0;
     int opt_fism_inplace = 1;            // 0: every row a round's users touch goes through the difference buffers (round 3's form)
     int opt_fism_lds = 1;                // 0: yue_fism_rounds always through k_fism_round (working rows in global memory, item lists from the host)
+    int64_t fism_form = 0;               // form the last yue_fism_rounds took: 0 k_fism_round, 1 k_fism_round_lds<KR, false>, 2 <KR, true> (read-only option fism_last_form)
     // exact path (chain_host.hip): touch keys / ordinals, runs, granule copies of the factor rows, control words
     DevBuf<uint32_t> ch_key, ch_val, ch_key2, ch_val2, ch_seg, ch_ord_i, ch_ord_j, ch_head, ch_incl, ch_ord_u, ch_rkey, ch_rval;
     DevBuf<int64_t> ch_run_ptr, d_ev_ptr;

@@ -86,6 +86,7 @@ const Option kOptions[] = {
     // FISM (fism_host.hip)
     {"fism_lds", YUE_AT(opt_fism_lds), set_flag},
     {"fism_inplace", YUE_AT(opt_fism_inplace), set_flag},
+    {"fism_last_form", YUE_AT(fism_form)},
     // S-rounds and epochs (bpr_host.hip), the communicator (comm.hip)
     {"round_stage", YUE_AT(opt_round_stage), set_ranged, 0, yue_host::kMetaStageMaxHost, "must be 0, 1 or 2..64"},
     {"round_last_stage_max", YUE_AT(last_stage_max)},
