@@ -34,7 +34,6 @@ struct yue_cnet {
     DevBuf<uint64_t> keep, cum;
     DevBuf<double> norm, sims;
     hipEvent_t ev[2] = {nullptr, nullptr};
-    int64_t last_ns = 0;
 };
 
 namespace yue_host {
@@ -50,14 +49,6 @@ void cnet_release(yue_ctx *c) {
     for (auto &e : k->ev) if (e) (void)hipEventDestroy(e);
     delete k;
     c->cnet = nullptr;
-}
-
-int cnet_set_option(yue_ctx *, const std::string &key, int64_t) { return fail(YUE_ERR_ARG, "yue_set_option: unknown option " + key); }
-
-int cnet_get_option(yue_ctx *c, const std::string &key, int64_t *value) {
-    if (key == "cnet_last_ns") *value = c->cnet ? c->cnet->last_ns : 0;        // device time of the last walks / embed / friends call
-    else return fail(YUE_ERR_ARG, "yue_get_option: unknown option " + key);
-    return YUE_OK;
 }
 
 }  // namespace yue_host
@@ -103,7 +94,7 @@ int stop_clock(yue_ctx *c, yue_cnet *k) {
     HIPCHK(hipStreamSynchronize(c->stream));
     float ms = 0.0f;
     HIPCHK(hipEventElapsedTime(&ms, k->ev[0], k->ev[1]));
-    k->last_ns = (int64_t)(1e6 * (double)ms);
+    c->cnet_ns = (int64_t)(1e6 * (double)ms);
     return YUE_OK;
 }
 

@@ -10,13 +10,13 @@
 
 using yue_host::fail;
 
+static_assert(yue_host::kCofRangeHost == yue::kCofRange, "the option table's upper end of cof_pass_items is the count kernel's range");
+
 struct yue_cof {
     // co-occurrence
     DevBuf<int64_t> co_ptr, row_nnz, cursor;
     DevBuf<int32_t> co_idx, co_cnt, events;
     int64_t co_n = -1, co_nnz = 0;
-    int64_t cooccur_mb = 1024;       // bound of the co-occurrence CSR (idx + cnt: 8 bytes per entry), MiB
-    int64_t pass_items = yue::kCofRange;   // items counted per pass
     // SPPMI and the level schedule
     DevBuf<int64_t> sp_ptr;
     DevBuf<int32_t> sp_idx;
@@ -38,8 +38,6 @@ struct yue_cof {
     DevBuf<int> status;
     hipEvent_t ev[2] = {nullptr, nullptr};
     std::vector<hipEvent_t> lev_ev;  // one in front of every level's launch and one behind the last
-    int64_t last_ns = 0, last_small_ns = 0;
-    int level_timing = 0;            // 1: time every level's launch (option cof_level_timing; tools/cofactor_bench.py)
 };
 
 namespace yue_host {
@@ -125,37 +123,8 @@ int ensure_schedule(yue_ctx *c, yue_cof *x, const yue_host::WrmfPairsView &v, in
 
 namespace yue_host {
 
-int cof_set_option(yue_ctx *c, const std::string &key, int64_t value) {
-    yue_cof *x = nullptr;
-    int rc = cof_state(c, &x);
-    if (rc) return rc;
-    if (key == "cof_cooccur_mb") {
-        if (value < 1 || value > 65536) return fail(YUE_ERR_ARG, "yue_set_option: cof_cooccur_mb must be in [1, 65536]");
-        x->cooccur_mb = value;
-    } else if (key == "cof_level_timing") {
-        if (value != 0 && value != 1) return fail(YUE_ERR_ARG, "yue_set_option: cof_level_timing must be 0 or 1");
-        x->level_timing = (int)value;
-    } else if (key == "cof_pass_items") {
-        if (value < 64 || value > yue::kCofRange) return fail(YUE_ERR_ARG, "yue_set_option: cof_pass_items must be in [64, " + std::to_string(yue::kCofRange) + "]");
-        x->pass_items = value;
-    } else {
-        return fail(YUE_ERR_ARG, "yue_set_option: unknown option " + key);
-    }
-    return YUE_OK;
-}
-
-int cof_get_option(yue_ctx *c, const std::string &key, int64_t *value) {
-    const yue_cof *x = c->cof;
-    if (key == "cof_cooccur_mb") *value = x ? x->cooccur_mb : 1024;
-    else if (key == "cof_level_timing") *value = x ? x->level_timing : 0;
-    else if (key == "cof_pass_items") *value = x ? x->pass_items : yue::kCofRange;
-    else if (key == "cof_last_ns") *value = x ? x->last_ns : 0;                   // device time of the last co-occurrence build / item sweep
-    else if (key == "cof_last_small_ns") *value = x ? x->last_small_ns : 0;       // ... of the sweep's levels of fewer than 256 rows (with cof_level_timing = 1, else 0)
-    else if (key == "cof_levels") *value = x ? x->levels : 0;                     // levels of the SPPMI of yue_cof_set_sppmi
-    else if (key == "cof_cooccur_nnz") *value = x && x->co_n >= 0 ? x->co_nnz : 0;
-    else return fail(YUE_ERR_ARG, "yue_get_option: unknown option " + key);
-    return YUE_OK;
-}
+int64_t cof_levels(const yue_ctx *c) { return c->cof ? c->cof->levels : 0; }     // of the SPPMI of yue_cof_set_sppmi
+int64_t cof_cooccur_nnz(const yue_ctx *c) { return c->cof && c->cof->co_n >= 0 ? c->cof->co_nnz : 0; }
 
 }  // namespace yue_host
 
@@ -181,7 +150,7 @@ int yue_cof_cooccur(yue_ctx *c, int filter, int64_t *nnz_out) {
     HIPCHK(x->co_ptr.resize((size_t)n + 1));
     yue::CofCoArgs a{};
     a.n = n; a.u_ptr = vu.ptr; a.u_items = vu.idx; a.i_ptr = vi.ptr; a.i_users = vi.idx; a.i_counts = vi.cnt;
-    a.cursor = x->cursor.p; a.events = x->events.p; a.filter = filter; a.range = (int)x->pass_items;
+    a.cursor = x->cursor.p; a.events = x->events.p; a.filter = filter; a.range = (int)c->opt_cof_pass_items;
     a.row_nnz = x->row_nnz.p; a.fill = 0;
     HIPCHK(hipEventRecord(x->ev[0], c->stream));
     hipLaunchKernelGGL(yue::k_cof_events, dim3((unsigned)((n + yue::kCofThreads - 1) / yue::kCofThreads)), dim3(yue::kCofThreads), 0, c->stream, a);
@@ -192,9 +161,9 @@ int yue_cof_cooccur(yue_ctx *c, int filter, int64_t *nnz_out) {
     HIPCHK(hipStreamSynchronize(c->stream));
     for (int64_t i = 0; i < n; ++i) ptr[(size_t)i + 1] += ptr[(size_t)i];
     const int64_t nnz = ptr[(size_t)n];
-    if (nnz > (x->cooccur_mb << 20) / 8)
+    if (nnz > (c->opt_cof_cooccur_mb << 20) / 8)
         return fail(YUE_ERR_ARG, "yue_cof_cooccur: the co-occurrence CSR holds " + std::to_string(nnz) + " entries, more than option cof_cooccur_mb = " +
-                                     std::to_string(x->cooccur_mb) + " MiB allows (8 bytes per entry): raise cof_cooccur_mb or the filter");
+                                     std::to_string(c->opt_cof_cooccur_mb) + " MiB allows (8 bytes per entry): raise cof_cooccur_mb or the filter");
     HIPCHK(x->co_idx.resize((size_t)std::max<int64_t>(nnz, 1)));
     HIPCHK(x->co_cnt.resize((size_t)std::max<int64_t>(nnz, 1)));
     HIPCHK(hipMemcpyAsync(x->co_ptr.p, ptr.data(), ((size_t)n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
@@ -205,7 +174,7 @@ int yue_cof_cooccur(yue_ctx *c, int filter, int64_t *nnz_out) {
     HIPCHK(hipStreamSynchronize(c->stream));
     float ms = 0.0f;
     HIPCHK(hipEventElapsedTime(&ms, x->ev[0], x->ev[1]));
-    x->last_ns = (int64_t)(1e6 * (double)ms);
+    c->cof_ns[0] = (int64_t)(1e6 * (double)ms);
     x->co_n = n;
     x->co_nnz = nnz;
     if (nnz_out) *nnz_out = nnz;
@@ -321,9 +290,8 @@ int yue_cof_item_sweep(yue_ctx *c, double alpha, double regU, double regR) {
     if (!x || x->sp_n != c->n) return fail(YUE_ERR_ARG, "yue_cof_item_sweep: call yue_cof_set_sppmi first (after yue_set_factors)");
     if (x->st_n != c->n || x->st_k != c->k) return fail(YUE_ERR_ARG, "yue_cof_item_sweep: call yue_cof_set_state first (G, w, c for the current n and k)");
     HIPCHK(hipSetDevice(c->device));
-    int64_t long_pairs = 0;
-    int rc = yue_host::wrmf_get_option(c, "wrmf_long_pairs", &long_pairs);
-    if (rc || (rc = ensure_schedule(c, x, v, long_pairs))) return rc;
+    int rc = ensure_schedule(c, x, v, c->opt_wrmf_long_pairs);
+    if (rc) return rc;
     const int k = c->k;
     yue::CofArgs a{};
     a.w.F = c->P.p; a.w.nf = c->m; a.w.X = c->Q.p; a.w.nr = c->n; a.w.k = k;
@@ -342,7 +310,7 @@ int yue_cof_item_sweep(yue_ctx *c, double alpha, double regU, double regR) {
     if (x->chunks > 0) hipLaunchKernelGGL(yue::k_cof_chunk, dim3((unsigned)x->chunks), dim3(yue::kWrmfThreads), 0, c->stream, a);
     const int lds = yue::wrmf_dyn_lds(k);
     HIPCHK(hipFuncSetAttribute((const void *)yue::k_cof_solve, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    const bool timed = x->level_timing != 0;
+    const bool timed = c->opt_cof_level_timing != 0;
     while (timed && (int64_t)x->lev_ev.size() < x->levels + 1) {
         hipEvent_t e;
         HIPCHK(hipEventCreate(&e));
@@ -362,14 +330,14 @@ int yue_cof_item_sweep(yue_ctx *c, double alpha, double regU, double regR) {
     HIPCHK(hipStreamSynchronize(c->stream));
     float ms = 0.0f;
     HIPCHK(hipEventElapsedTime(&ms, x->ev[0], x->ev[1]));
-    x->last_ns = (int64_t)(1e6 * (double)ms);
+    c->cof_ns[0] = (int64_t)(1e6 * (double)ms);
     double small_ms = 0.0;
     for (int64_t l = 0; timed && l < x->levels; ++l)
         if (x->level_ptr[(size_t)l + 1] - x->level_ptr[(size_t)l] < 256) {
             HIPCHK(hipEventElapsedTime(&ms, x->lev_ev[(size_t)l], x->lev_ev[(size_t)l + 1]));
             small_ms += (double)ms;
         }
-    x->last_small_ns = (int64_t)(1e6 * small_ms);
+    c->cof_ns[1] = (int64_t)(1e6 * small_ms);
     if (status != INT_MAX)
         return fail(YUE_ERR_ARG, "yue_cof_item_sweep: non-positive pivot in a Cholesky factorisation of item row " + std::to_string(status) +
                                      " (raise regU or regR)");

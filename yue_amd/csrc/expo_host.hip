@@ -16,8 +16,6 @@ struct yue_expo {
     int64_t n_mu = 0;
     hipEvent_t ev[2] = {nullptr, nullptr};
     std::vector<std::pair<hipEvent_t, hipEvent_t>> gram_ev;     // brackets of the Gram launches of the last half-sweep
-    int64_t last_ns = 0, last_gram_ns = 0, last_batches = 0;
-    int64_t gram_mb = 512;           // budget of the per-row Gram workspace, MiB: a half-sweep runs in batches of rows that fit
 };
 
 namespace yue_host {
@@ -106,32 +104,6 @@ int common_checks(yue_ctx *c, const char *who, yue_expo **x, double lam_y) {
 
 }  // namespace
 
-namespace yue_host {
-
-int expo_set_option(yue_ctx *c, const std::string &key, int64_t value) {
-    if (key == "expo_gram_mb") {
-        if (value < 1 || value > 65536) return fail(YUE_ERR_ARG, "yue_set_option: expo_gram_mb must be in [1, 65536]");
-        yue_expo *x = nullptr;
-        int rc = expo_state(c, &x);
-        if (rc) return rc;
-        x->gram_mb = value;
-        return YUE_OK;
-    }
-    return fail(YUE_ERR_ARG, "yue_set_option: unknown option " + key);
-}
-
-int expo_get_option(yue_ctx *c, const std::string &key, int64_t *value) {
-    const yue_expo *x = c->expo;
-    if (key == "expo_gram_mb") *value = x ? x->gram_mb : 512;
-    else if (key == "expo_last_ns") *value = x ? x->last_ns : 0;                 // device time of the last half-sweep / mu update
-    else if (key == "expo_last_gram_ns") *value = x ? x->last_gram_ns : 0;       // ... of its dense MFMA kernel(s)
-    else if (key == "expo_last_batches") *value = x ? x->last_batches : 0;       // row batches of the last half-sweep
-    else return fail(YUE_ERR_ARG, "yue_get_option: unknown option " + key);
-    return YUE_OK;
-}
-
-}  // namespace yue_host
-
 extern "C" {
 
 int yue_expo_set_pairs(yue_ctx *c, const int64_t *u_ptr, const int32_t *u_items, const int32_t *u_counts,
@@ -186,7 +158,7 @@ int yue_expo_half_sweep(yue_ctx *c, int side, double lam, double lam_y, int mu_p
     const int64_t tiles_all = g.tiles_all;
     a.npairs = g.npairs; a.splits = g.splits; a.cols_per_split = g.cols_per_split;
     // rows per batch: the workspace [splits][rows][npairs] fp32 within the budget, a multiple of the tile
-    int64_t rows_batch = (x->gram_mb << 20) / ((int64_t)a.splits * a.npairs * 4);
+    int64_t rows_batch = (c->opt_expo_gram_mb << 20) / ((int64_t)a.splits * a.npairs * 4);
     rows_batch = std::max<int64_t>(yue::kExpoTile, rows_batch / yue::kExpoTile * yue::kExpoTile);
     rows_batch = std::min<int64_t>(rows_batch, tiles_all * yue::kExpoTile);
     HIPCHK(x->gws.resize((size_t)a.splits * (size_t)rows_batch * (size_t)a.npairs));
@@ -226,14 +198,14 @@ int yue_expo_half_sweep(yue_ctx *c, int side, double lam, double lam_y, int mu_p
     HIPCHK(hipStreamSynchronize(c->stream));
     float ms = 0.0f;
     HIPCHK(hipEventElapsedTime(&ms, x->ev[0], x->ev[1]));
-    x->last_ns = (int64_t)(1e6 * (double)ms);
+    c->expo_ns[0] = (int64_t)(1e6 * (double)ms);
     double gram_ms = 0.0;
     for (int64_t b = 0; b < batches; ++b) {
         HIPCHK(hipEventElapsedTime(&ms, x->gram_ev[(size_t)b].first, x->gram_ev[(size_t)b].second));
         gram_ms += (double)ms;
     }
-    x->last_gram_ns = (int64_t)(1e6 * gram_ms);
-    x->last_batches = batches;
+    c->expo_ns[1] = (int64_t)(1e6 * gram_ms);
+    c->expo_batches = batches;
     if (status != INT_MAX)
         return fail(YUE_ERR_ARG, std::string("yue_expo_half_sweep: non-positive pivot in the Cholesky factorisation of ") + (side == 0 ? "user" : "item") +
                                      " row " + std::to_string(status) + " (B = F^T diag(A) F + lam*I is not positive definite: raise lam)");
@@ -261,7 +233,7 @@ int yue_expo_gram_rows(yue_ctx *c, int side, int mu_per_column, double lam_y, co
     const GramPlan g = gram_plan(k, v.rows, a.nf);
     a.npairs = g.npairs; a.splits = g.splits; a.cols_per_split = g.cols_per_split;
     const size_t cells = (size_t)a.splits * (size_t)nrows * (size_t)a.npairs;
-    if (cells * 4 > ((size_t)x->gram_mb << 20)) return fail(YUE_ERR_ARG, "yue_expo_gram_rows: the list's Grams do not fit expo_gram_mb");
+    if (cells * 4 > ((size_t)c->opt_expo_gram_mb << 20)) return fail(YUE_ERR_ARG, "yue_expo_gram_rows: the list's Grams do not fit expo_gram_mb");
     HIPCHK(x->gws.resize(cells));
     HIPCHK(x->rows.resize((size_t)nrows));
     HIPCHK(hipMemcpyAsync(x->rows.p, rows, (size_t)nrows * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
@@ -309,8 +281,8 @@ int yue_expo_update_mu(yue_ctx *c, double pa, double pb, double lam_y) {
     HIPCHK(hipStreamSynchronize(c->stream));
     float ms = 0.0f;
     HIPCHK(hipEventElapsedTime(&ms, x->ev[0], x->ev[1]));
-    x->last_ns = (int64_t)(1e6 * (double)ms);
-    x->last_gram_ns = 0;
+    c->expo_ns[0] = (int64_t)(1e6 * (double)ms);
+    c->expo_ns[1] = 0;
     return YUE_OK;
 }
 

@@ -3,7 +3,7 @@
 //   core_host.hip   context, factors, interactions            bpr_host.hip   replay levels, S-rounds, epochs, CUNE, Adam, kernel timing
 //   chain_host.hip  exact sequential semantics as dataflow    scan_host.hip  predict + evalRanking's selection, scan statistics
 //   fism_host.hip   FISM                                      comm.hip       RCCL
-//   options_host.hip  yue_get_option / yue_set_option: the option table (no device code)
+//   options_host.hip  yue_get_option / yue_set_option: one table row per option, every subsystem's included (no device code)
 //   wrmf_host.hip   WRMF (ALS half-sweeps)                     knn_host.hip   UserKNN (neighbours, ranking)
 //   ipf_host.hip    IPF (session-graph ranking)                expo_host.hip  ExpoMF (exposure-weighted ALS, MFMA Gram)
 //   cof_host.hip    CoFactor (co-occurrence, level-scheduled item sweep)
@@ -69,6 +69,10 @@ struct DevBuf {
 constexpr int kNllSlotsHost = 1024;   // == yue::kNllSlots (bpr_device.hpp; checked where both are visible)
 constexpr int kHeaderSlackHost = 16;  // == yue::kHeaderSlack (round_kernels.hpp)
 constexpr int kMetaStageMaxHost = 64; // == yue::kMetaStageMax (round_kernels.hpp)
+// ends of option ranges (options_host.hip includes no kernel header), each checked in the subsystem's own unit
+constexpr int kWrmfStageHost = 32;    // == yue::kWrmfStage (wrmf_kernels.hpp)
+constexpr int kKnnRangeHost = 4096, kKnnMaxKHost = 256, kKnnGatherHost = 2048;   // == yue::kKnnRange, kKnnMaxK, kKnnGather (knn_kernels.hpp)
+constexpr int kCofRangeHost = 8192;   // == yue::kCofRange (cof_kernels.hpp)
 
 inline int kr_of(int k) { return k <= 64 ? 1 : k <= 128 ? 2 : 4; }   // registers per lane per row (64 lanes)
 
@@ -218,12 +222,28 @@ struct yue_ctx {
     int comm_version = 0, comm_nranks_reported = 0;
     hipEvent_t ev_scan0 = nullptr, ev_scan1 = nullptr;      // brackets of the scoring kernel (yue_get_scan_stats)
     yue_wrmf *wrmf = nullptr;            // WRMF state (yue_wrmf_set_pairs), owned by wrmf_host.hip
+    int64_t opt_wrmf_long_pairs = 2048;  // WRMF: rows with more pairs are summed by several workgroups (chunks of this many pairs) before their solve; read by yue_wrmf_set_pairs and by CoFactor's schedule
+    int64_t wrmf_ns[2] = {0, 0};         // device time of the last half-sweep, of its long-row chunks (read-only options wrmf_last_ns / wrmf_last_long_ns)
     yue_knn *knn = nullptr;              // UserKNN state (yue_knn_set_pairs), owned by knn_host.hip
+    int opt_knn_range = yue_host::kKnnRangeHost, opt_knn_gather = yue_host::kKnnGatherHost;   // UserKNN: candidate users per counting pass, entries per scoring chunk (tests lower them to reach the multi-pass paths)
+    int64_t knn_ns = 0, knn_chunked_users = 0;   // device time of the last neighbours / topn / predict call; users of the last topn scored in item-range chunks (read-only options knn_last_*)
     yue_ipf *ipf = nullptr;              // IPF state (yue_ipf_set_graph), owned by ipf_host.hip
+    int opt_ipf_slots = 1024;            // IPF: workgroups (queries in flight) of one yue_ipf_topn launch
+    int64_t ipf_ns = 0;                  // device time of the last topn / predict launch (read-only option ipf_last_ns)
     yue_expo *expo = nullptr;            // ExpoMF state (yue_expo_set_mu), owned by expo_host.hip
+    int64_t opt_expo_gram_mb = 512;      // ExpoMF: budget of the per-row Gram workspace, MiB: a half-sweep runs in batches of rows that fit
+    int64_t expo_ns[2] = {0, 0};         // device time of the last half-sweep / mu update, of its dense MFMA kernel(s) (read-only options expo_last_ns / expo_last_gram_ns)
+    int64_t expo_batches = 0;            // row batches of the last half-sweep (read-only option expo_last_batches)
     yue_cof *cof = nullptr;              // CoFactor state (yue_cof_*), owned by cof_host.hip
+    int64_t opt_cof_cooccur_mb = 1024;   // CoFactor: bound of the co-occurrence CSR (idx + cnt: 8 bytes per entry), MiB
+    int64_t opt_cof_pass_items = yue_host::kCofRangeHost;   // ... items counted per pass
+    int opt_cof_level_timing = 0;        // ... 1: time every level's launch (tools/cofactor_bench.py)
+    int64_t cof_ns[2] = {0, 0};          // device time of the last co-occurrence build / item sweep, of the sweep's levels of fewer than 256 rows (0 unless timed) (read-only options cof_last_ns / cof_last_small_ns)
     yue_cnet *cnet = nullptr;            // CUNE user-network state (yue_cnet_*), owned by cnet_host.hip
+    int64_t cnet_ns = 0;                 // device time of the last walks / embed / friends call (read-only option cnet_last_ns)
     yue_s2v *s2v = nullptr;              // Song2vec state (yue_s2v_*), owned by s2v_host.hip
+    int opt_s2v_schedule = 1;            // Song2vec: 0 = one wave walks all steps, 1 = one launch per dependency level
+    int64_t s2v_ns = 0;                  // device time of the last yue_s2v_epoch (read-only option s2v_last_ns)
     yue_lgcn *lgcn = nullptr;            // LightGCN state (yue_lgcn_*), owned by lgcn_host.hip
     int64_t opt_lgcn_hub = 1024;         // LightGCN: rows with more neighbours are cut into parts of this many, one wave each (lgcn_kernels.hpp)
     int64_t lgcn_hubs = 0, lgcn_parts = 0;   // ... such rows and their parts in the last call (read-only options lgcn_last_hubs / lgcn_last_parts)
@@ -256,10 +276,10 @@ int reduce_user_block(yue_ctx *c, int64_t first, int64_t count, hipStream_t stre
 // chain_host.hip: exact sequential semantics over the uploaded events (negatives in ev_j) / over the stream in xu, xi, xj
 int chain_epoch(yue_ctx *c, double lr, double regU, double regI);
 int chain_stream(yue_ctx *c, int64_t T, double lr, double regU, double regI);
-// wrmf_host.hip: frees the WRMF state; options "wrmf_*" (returns 1 when `key` is not one of them)
+// The subsystems below: what yue_get_option reads from one of them without a state is 0.
+// wrmf_host.hip: frees the WRMF state; a side's long rows (read-only options wrmf_long_rows_user / _item)
 void wrmf_release(yue_ctx *c);
-int wrmf_set_option(yue_ctx *c, const std::string &key, int64_t value);
-int wrmf_get_option(yue_ctx *c, const std::string &key, int64_t *value);
+int64_t wrmf_long_rows(const yue_ctx *c, int side);
 // ... the uploaded pairs of one side (0: user rows, 1: item rows) for the other ALS solver (expo_host.hip); false when
 // yue_wrmf_set_pairs has not run for the context's current factors
 struct WrmfPairsView {
@@ -272,30 +292,20 @@ bool wrmf_pairs_view(const yue_ctx *c, int side, WrmfPairsView *v);
 // ... and the fp32-rounded F^T F of the side's fixed factors (0: Y^T Y, 1: X^T X), queued on the context's stream into the
 // WRMF state's slot-major buffer (cof_host.hip)
 int wrmf_gram(yue_ctx *c, int side, const double **G);
-// knn_host.hip: frees the UserKNN state; options "knn_*"
+// knn_host.hip, ipf_host.hip, expo_host.hip, cnet_host.hip: free the subsystem's state
 void knn_release(yue_ctx *c);
-int knn_set_option(yue_ctx *c, const std::string &key, int64_t value);
-int knn_get_option(yue_ctx *c, const std::string &key, int64_t *value);
-// ipf_host.hip: frees the IPF state; options "ipf_*"
 void ipf_release(yue_ctx *c);
-int ipf_set_option(yue_ctx *c, const std::string &key, int64_t value);
-int ipf_get_option(yue_ctx *c, const std::string &key, int64_t *value);
-// expo_host.hip: frees the ExpoMF state; options "expo_*"
 void expo_release(yue_ctx *c);
-int expo_set_option(yue_ctx *c, const std::string &key, int64_t value);
-int expo_get_option(yue_ctx *c, const std::string &key, int64_t *value);
-// cof_host.hip: frees the CoFactor state; options "cof_*"
-void cof_release(yue_ctx *c);
-int cof_set_option(yue_ctx *c, const std::string &key, int64_t value);
-int cof_get_option(yue_ctx *c, const std::string &key, int64_t *value);
-// cnet_host.hip: frees the user-network state; options "cnet_*"
 void cnet_release(yue_ctx *c);
-int cnet_set_option(yue_ctx *c, const std::string &key, int64_t value);
-int cnet_get_option(yue_ctx *c, const std::string &key, int64_t *value);
-// s2v_host.hip: frees the Song2vec state; options "s2v_*"
+// cof_host.hip: frees the CoFactor state; levels of the uploaded SPPMI, entries of the co-occurrence CSR (read-only options
+// cof_levels / cof_cooccur_nnz)
+void cof_release(yue_ctx *c);
+int64_t cof_levels(const yue_ctx *c);
+int64_t cof_cooccur_nnz(const yue_ctx *c);
+// s2v_host.hip: frees the Song2vec state; dependency levels of the steps (which = 0) / the pairs (1) (read-only options
+// s2v_levels_steps / s2v_levels_pairs)
 void s2v_release(yue_ctx *c);
-int s2v_set_option(yue_ctx *c, const std::string &key, int64_t value);
-int s2v_get_option(yue_ctx *c, const std::string &key, int64_t *value);
+int64_t s2v_levels(const yue_ctx *c, int which);
 // lgcn_host.hip: frees the LightGCN state (its options are rows of the option table)
 void lgcn_release(yue_ctx *c);
 // ngcf_host.hip: frees the NGCF state (its options are rows of the option table)

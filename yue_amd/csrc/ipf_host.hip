@@ -19,8 +19,6 @@ struct yue_ipf {
     DevBuf<double> r2u, r2s, score, scores_out;
     DevBuf<int32_t> touch2, touch3, users, ids_out, len_out;
     hipEvent_t ev[2] = {nullptr, nullptr};
-    int64_t last_ns = 0;
-    int opt_slots = 1024;                    // option ipf_slots: workgroups (queries in flight) of one yue_ipf_topn launch
 };
 
 namespace yue_host {
@@ -129,7 +127,7 @@ int finish(yue_ctx *c, yue_ipf *g) {
     HIPCHK(hipStreamSynchronize(c->stream));
     float ms = 0.0f;
     HIPCHK(hipEventElapsedTime(&ms, g->ev[0], g->ev[1]));
-    g->last_ns = (int64_t)(1e6 * (double)ms);
+    c->ipf_ns = (int64_t)(1e6 * (double)ms);
     g->clean = true;
     return YUE_OK;
 }
@@ -142,30 +140,6 @@ int ready(yue_ctx *c, const char *who, yue_ipf **out) {
 }
 
 }  // namespace
-
-namespace yue_host {
-
-int ipf_set_option(yue_ctx *c, const std::string &key, int64_t value) {
-    yue_ipf *g = nullptr;
-    if (key == "ipf_slots") {
-        if (value < 1 || value > 4096) return fail(YUE_ERR_ARG, "yue_set_option: ipf_slots must be 1..4096");
-        int rc = ipf_state(c, &g);
-        if (rc) return rc;
-        g->opt_slots = (int)value;
-        return YUE_OK;
-    }
-    return fail(YUE_ERR_ARG, "yue_set_option: unknown option " + key);
-}
-
-int ipf_get_option(yue_ctx *c, const std::string &key, int64_t *value) {
-    const yue_ipf *g = c->ipf;
-    if (key == "ipf_slots") *value = g ? g->opt_slots : 1024;
-    else if (key == "ipf_last_ns") *value = g ? g->last_ns : 0;          // device time of the last topn / predict launch
-    else return fail(YUE_ERR_ARG, "yue_get_option: unknown option " + key);
-    return YUE_OK;
-}
-
-}  // namespace yue_host
 
 extern "C" {
 
@@ -224,9 +198,9 @@ int yue_ipf_topn(yue_ctx *c, const int32_t *users, int64_t nu, int N, int32_t *i
     HIPCHK(g->users.resize((size_t)nu)); HIPCHK(g->ids_out.resize((size_t)nu * N)); HIPCHK(g->scores_out.resize((size_t)nu * N));
     HIPCHK(g->len_out.resize((size_t)nu)); HIPCHK(g->ins_out.resize(1));
     HIPCHK(hipMemcpyAsync(g->users.p, users, (size_t)nu * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    // slots: at most opt_slots, and at most 4 GiB of work arrays
+    // slots: at most the option ipf_slots, and at most 4 GiB of work arrays
     const int64_t per_slot = 36 * g->m + 28 * g->n;
-    const int64_t slots = std::max<int64_t>(1, std::min<int64_t>({nu, (int64_t)g->opt_slots, ((int64_t)4 << 30) / per_slot}));
+    const int64_t slots = std::max<int64_t>(1, std::min<int64_t>({nu, (int64_t)c->opt_ipf_slots, ((int64_t)4 << 30) / per_slot}));
     if ((rc = launch(c, g, nu, N, slots))) return rc;
     HIPCHK(hipMemcpyAsync(ids_out, g->ids_out.p, (size_t)nu * N * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(scores_out, g->scores_out.p, (size_t)nu * N * sizeof(double), hipMemcpyDeviceToHost, c->stream));

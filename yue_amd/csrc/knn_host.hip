@@ -8,6 +8,9 @@
 
 using yue_host::fail;
 
+static_assert(yue_host::kKnnRangeHost == yue::kKnnRange && yue_host::kKnnMaxKHost == yue::kKnnMaxK && yue_host::kKnnGatherHost == yue::kKnnGather,
+              "the option table's ends of knn_range and knn_gather are the kernels' widths");
+
 struct yue_knn {
     int64_t m = 0, n = 0, nnz = 0;
     DevBuf<int64_t> u_ptr, i_ptr, cursor;
@@ -18,9 +21,6 @@ struct yue_knn {
     DevBuf<double> scores;
     DevBuf<int> chunked;
     hipEvent_t ev[2] = {nullptr, nullptr};
-    int64_t last_ns = 0, last_chunked = 0;
-    int range = yue::kKnnRange;              // options knn_range / knn_gather (tests lower them to reach the multi-pass paths)
-    int gather = yue::kKnnGather;
 };
 
 namespace yue_host {
@@ -74,12 +74,12 @@ int upload(DevBuf<T> &buf, const T *src, int64_t count) {
     return YUE_OK;
 }
 
-yue::KnnArgs base_args(const yue_knn *k) {
+yue::KnnArgs base_args(const yue_ctx *c, const yue_knn *k) {
     yue::KnnArgs a{};
     a.m = k->m; a.n = k->n;
     a.u_ptr = k->u_ptr.p; a.u_items = k->u_items.p; a.u_counts = k->u_counts.p;
     a.i_ptr = k->i_ptr.p; a.i_users = k->i_users.p;
-    a.K = k->K; a.range = k->range; a.gather = k->gather;
+    a.K = k->K; a.range = c->opt_knn_range; a.gather = c->opt_knn_gather;
     a.nbr = k->nbr.p; a.inter = k->inter.p; a.uni = k->uni.p;
     return a;
 }
@@ -93,39 +93,6 @@ int ready(yue_ctx *c, const char *who, yue_knn **out) {
 }
 
 }  // namespace
-
-namespace yue_host {
-
-int knn_set_option(yue_ctx *c, const std::string &key, int64_t value) {
-    yue_knn *k = nullptr;
-    if (key == "knn_range") {
-        if (value < 64 || value > yue::kKnnRange) return fail(YUE_ERR_ARG, "yue_set_option: knn_range must be 64..4096");
-        int rc = knn_state(c, &k);
-        if (rc) return rc;
-        k->range = (int)value;
-        return YUE_OK;
-    }
-    if (key == "knn_gather") {
-        if (value < yue::kKnnMaxK || value > yue::kKnnGather) return fail(YUE_ERR_ARG, "yue_set_option: knn_gather must be 256..2048");
-        int rc = knn_state(c, &k);
-        if (rc) return rc;
-        k->gather = (int)value;
-        return YUE_OK;
-    }
-    return fail(YUE_ERR_ARG, "yue_set_option: unknown option " + key);
-}
-
-int knn_get_option(yue_ctx *c, const std::string &key, int64_t *value) {
-    const yue_knn *k = c->knn;
-    if (key == "knn_range") *value = k ? k->range : yue::kKnnRange;
-    else if (key == "knn_gather") *value = k ? k->gather : yue::kKnnGather;
-    else if (key == "knn_last_ns") *value = k ? k->last_ns : 0;                     // device time of the last neighbours / topn / predict call
-    else if (key == "knn_last_chunked_users") *value = k ? k->last_chunked : 0;     // users of the last topn scored in item-range chunks
-    else return fail(YUE_ERR_ARG, "yue_get_option: unknown option " + key);
-    return YUE_OK;
-}
-
-}  // namespace yue_host
 
 extern "C" {
 
@@ -171,7 +138,7 @@ int yue_knn_neighbors(yue_ctx *c, int K, int32_t *nbr_out, int32_t *inter_out, i
     const size_t cells = (size_t)k->m * (size_t)K;
     HIPCHK(k->nbr.resize(cells)); HIPCHK(k->inter.resize(cells)); HIPCHK(k->uni.resize(cells));
     k->K = K;
-    yue::KnnArgs a = base_args(k);
+    yue::KnnArgs a = base_args(c, k);
     a.cursor = k->cursor.p;
     HIPCHK(hipEventRecord(k->ev[0], c->stream));
     hipLaunchKernelGGL(yue::k_knn_neighbors, dim3((unsigned)k->m), dim3(yue::kKnnThreads), 0, c->stream, a);
@@ -183,7 +150,7 @@ int yue_knn_neighbors(yue_ctx *c, int K, int32_t *nbr_out, int32_t *inter_out, i
     HIPCHK(hipStreamSynchronize(c->stream));
     float ms = 0.0f;
     HIPCHK(hipEventElapsedTime(&ms, k->ev[0], k->ev[1]));
-    k->last_ns = (int64_t)(1e6 * (double)ms);
+    c->knn_ns = (int64_t)(1e6 * (double)ms);
     return YUE_OK;
 }
 
@@ -201,7 +168,7 @@ int yue_knn_topn(yue_ctx *c, const int32_t *users, int64_t nu, int N, int32_t *i
     HIPCHK(k->users.resize((size_t)nu)); HIPCHK(k->ids.resize((size_t)nu * N)); HIPCHK(k->scores.resize((size_t)nu * N)); HIPCHK(k->len.resize((size_t)nu));
     HIPCHK(hipMemcpyAsync(k->users.p, users, (size_t)nu * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemsetAsync(k->chunked.p, 0, sizeof(int), c->stream));
-    yue::KnnArgs a = base_args(k);
+    yue::KnnArgs a = base_args(c, k);
     a.users = k->users.p; a.N = N; a.exclude_own = 1;
     a.ids_out = k->ids.p; a.scores_out = k->scores.p; a.len_out = k->len.p; a.chunked_users = k->chunked.p;
     HIPCHK(hipEventRecord(k->ev[0], c->stream));
@@ -216,8 +183,8 @@ int yue_knn_topn(yue_ctx *c, const int32_t *users, int64_t nu, int N, int32_t *i
     HIPCHK(hipStreamSynchronize(c->stream));
     float ms = 0.0f;
     HIPCHK(hipEventElapsedTime(&ms, k->ev[0], k->ev[1]));
-    k->last_ns = (int64_t)(1e6 * (double)ms);
-    k->last_chunked = chunked;
+    c->knn_ns = (int64_t)(1e6 * (double)ms);
+    c->knn_chunked_users = chunked;
     return YUE_OK;
 }
 
@@ -229,7 +196,7 @@ int yue_knn_predict(yue_ctx *c, int32_t user, int64_t cap, int32_t *items_out, d
     if (cap < 0 || (cap > 0 && (!items_out || !scores_out)) || !len_out) return fail(YUE_ERR_ARG, "yue_knn_predict: need cap >= 0 and non-null arrays");
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(k->scores.resize((size_t)k->n));
-    yue::KnnArgs a = base_args(k);
+    yue::KnnArgs a = base_args(c, k);
     a.user = user; a.item_scores = k->scores.p;
     HIPCHK(hipEventRecord(k->ev[0], c->stream));
     hipLaunchKernelGGL(yue::k_knn_predict_scores, dim3((unsigned)((k->n + yue::kKnnThreads - 1) / yue::kKnnThreads)), dim3(yue::kKnnThreads), 0, c->stream, a);
@@ -240,7 +207,7 @@ int yue_knn_predict(yue_ctx *c, int32_t user, int64_t cap, int32_t *items_out, d
     HIPCHK(hipStreamSynchronize(c->stream));
     float ms = 0.0f;
     HIPCHK(hipEventElapsedTime(&ms, k->ev[0], k->ev[1]));
-    k->last_ns = (int64_t)(1e6 * (double)ms);
+    c->knn_ns = (int64_t)(1e6 * (double)ms);
     // the one-user list: the scored items by (score descending, item ascending)
     std::vector<int32_t> order;
     for (int64_t i = 0; i < k->n; ++i)

@@ -1,6 +1,6 @@
-// libyue_hip.so -- yue_get_option / yue_set_option (include/yue_hip.h): one table row per option of the context, walked by
-// both entry points.  The subsystems with a state of their own (wrmf_, knn_, ipf_, expo_, cof_, cnet_, s2v_) keep their options and are
-// routed by prefix.  No kernel header is included: this unit holds no device code.
+// libyue_hip.so -- yue_get_option / yue_set_option (include/yue_hip.h): one table row per option, walked by both entry
+// points.  Every option is a member of the context, or a fact that a subsystem's own reader returns (0 without a state), so
+// no call here allocates or touches a subsystem.  No kernel header is included: this unit holds no device code.
 #include "host_common.hpp"
 
 #include <limits>
@@ -20,6 +20,8 @@ struct Option {
 };
 // get and put of an option kept in a member of the context (int and int64_t members both occur)
 #define YUE_AT(member) [](yue_ctx *c) -> int64_t { return c->member; }, [](yue_ctx *c, int64_t v) { c->member = (decltype(c->member))v; }
+// get of a fact a subsystem keeps for its own logic
+#define YUE_FROM(reader) [](yue_ctx *c) -> int64_t { return yue_host::reader; }
 
 int set_flag(const Option &o, yue_ctx *c, int64_t value) { o.put(c, value != 0); return YUE_OK; }
 
@@ -69,6 +71,8 @@ int set_round_tpw(const Option &, yue_ctx *c, int64_t value) {
 int set_stamp_launch(const Option &, yue_ctx *c, int64_t value) { c->stamp_launch = value; c->update_launches = 0; return YUE_OK; }
 #endif
 
+constexpr int64_t kNoEnd = std::numeric_limits<int64_t>::max();
+
 const Option kOptions[] = {
     // scoring (scan_host.hip)
     {"scan_f32", YUE_AT(opt_scan_f32), set_flag},
@@ -78,7 +82,7 @@ const Option kOptions[] = {
     {"scan_filter_ub", YUE_AT(opt_scan_filter_ub), set_ranged, 1, 3, "must be 1, 2 or 3"},
     {"scan_streams", YUE_AT(opt_scan_streams), set_ranged, 1, 2, "must be 1 or 2"},
     {"scan_slabs", YUE_AT(opt_scan_slabs), set_ranged, 2, 64, "must be 2..64"},
-    {"scan_streams_min_users", YUE_AT(opt_scan_streams_min_users), set_ranged, 1024, std::numeric_limits<int64_t>::max(), "must be at least 1024"},
+    {"scan_streams_min_users", YUE_AT(opt_scan_streams_min_users), set_ranged, 1024, kNoEnd, "must be at least 1024"},
     {"scan_last_chunks", YUE_AT(scan_chunks)},
     {"scan_last_few_users", YUE_AT(scan_few_users)},
     {"scan_last_settle", YUE_AT(scan_settle)},
@@ -140,8 +144,43 @@ const Option kOptions[] = {
     {"cdae_last_hubs", YUE_AT(cdae_hubs)},
     {"cdae_last_parts", YUE_AT(cdae_parts)},
     {"cdae_last_saturated", YUE_AT(cdae_saturated)},
+    // WRMF (wrmf_host.hip)
+    {"wrmf_long_pairs", YUE_AT(opt_wrmf_long_pairs), set_ranged, yue_host::kWrmfStageHost, kNoEnd, "must be >= 32"},   // takes effect at the next yue_wrmf_set_pairs
+    {"wrmf_last_ns", YUE_AT(wrmf_ns[0])},
+    {"wrmf_last_long_ns", YUE_AT(wrmf_ns[1])},
+    {"wrmf_long_rows_user", YUE_FROM(wrmf_long_rows(c, 0))},
+    {"wrmf_long_rows_item", YUE_FROM(wrmf_long_rows(c, 1))},
+    // UserKNN (knn_host.hip)
+    {"knn_range", YUE_AT(opt_knn_range), set_ranged, 64, yue_host::kKnnRangeHost, "must be 64..4096"},
+    {"knn_gather", YUE_AT(opt_knn_gather), set_ranged, yue_host::kKnnMaxKHost, yue_host::kKnnGatherHost, "must be 256..2048"},
+    {"knn_last_ns", YUE_AT(knn_ns)},
+    {"knn_last_chunked_users", YUE_AT(knn_chunked_users)},
+    // IPF (ipf_host.hip)
+    {"ipf_slots", YUE_AT(opt_ipf_slots), set_ranged, 1, 4096, "must be 1..4096"},
+    {"ipf_last_ns", YUE_AT(ipf_ns)},
+    // ExpoMF (expo_host.hip)
+    {"expo_gram_mb", YUE_AT(opt_expo_gram_mb), set_ranged, 1, 65536, "must be in [1, 65536]"},
+    {"expo_last_ns", YUE_AT(expo_ns[0])},
+    {"expo_last_gram_ns", YUE_AT(expo_ns[1])},
+    {"expo_last_batches", YUE_AT(expo_batches)},
+    // CoFactor (cof_host.hip)
+    {"cof_cooccur_mb", YUE_AT(opt_cof_cooccur_mb), set_ranged, 1, 65536, "must be in [1, 65536]"},
+    {"cof_level_timing", YUE_AT(opt_cof_level_timing), set_ranged, 0, 1, "must be 0 or 1"},
+    {"cof_pass_items", YUE_AT(opt_cof_pass_items), set_ranged, 64, yue_host::kCofRangeHost, "must be in [64, 8192]"},
+    {"cof_last_ns", YUE_AT(cof_ns[0])},
+    {"cof_last_small_ns", YUE_AT(cof_ns[1])},
+    {"cof_levels", YUE_FROM(cof_levels(c))},
+    {"cof_cooccur_nnz", YUE_FROM(cof_cooccur_nnz(c))},
+    // CUNE's user-network stage (cnet_host.hip)
+    {"cnet_last_ns", YUE_AT(cnet_ns)},
+    // Song2vec (s2v_host.hip)
+    {"s2v_schedule", YUE_AT(opt_s2v_schedule), set_ranged, 0, 1, "must be 0 (one wave walks all steps) or 1 (levels)"},
+    {"s2v_levels_steps", YUE_FROM(s2v_levels(c, 0))},
+    {"s2v_levels_pairs", YUE_FROM(s2v_levels(c, 1))},
+    {"s2v_last_ns", YUE_AT(s2v_ns)},
 };
 #undef YUE_AT
+#undef YUE_FROM
 
 const Option *find_option(const std::string &key) {
     for (const Option &o : kOptions) if (key == o.name) return &o;
@@ -157,13 +196,6 @@ int yue_get_option(yue_ctx *c, const char *name, int64_t *value) {
     const std::string key(name);
     const Option *o = find_option(key);
     if (o && o->get) { *value = o->get(c); return YUE_OK; }
-    if (key.compare(0, 5, "wrmf_") == 0) return yue_host::wrmf_get_option(c, key, value);
-    if (key.compare(0, 4, "knn_") == 0) return yue_host::knn_get_option(c, key, value);
-    if (key.compare(0, 4, "ipf_") == 0) return yue_host::ipf_get_option(c, key, value);
-    if (key.compare(0, 5, "expo_") == 0) return yue_host::expo_get_option(c, key, value);
-    if (key.compare(0, 4, "cof_") == 0) return yue_host::cof_get_option(c, key, value);
-    if (key.compare(0, 5, "cnet_") == 0) return yue_host::cnet_get_option(c, key, value);
-    if (key.compare(0, 4, "s2v_") == 0) return yue_host::s2v_get_option(c, key, value);
     return fail(YUE_ERR_ARG, "yue_get_option: unknown option " + key);
 }
 
@@ -172,13 +204,6 @@ int yue_set_option(yue_ctx *c, const char *name, int64_t value) {
     const std::string key(name);
     const Option *o = find_option(key);
     if (o && o->set) return o->set(*o, c, value);          // (a read-only name answers as one the table does not hold)
-    if (key.compare(0, 5, "wrmf_") == 0) return yue_host::wrmf_set_option(c, key, value);
-    if (key.compare(0, 4, "knn_") == 0) return yue_host::knn_set_option(c, key, value);
-    if (key.compare(0, 4, "ipf_") == 0) return yue_host::ipf_set_option(c, key, value);
-    if (key.compare(0, 5, "expo_") == 0) return yue_host::expo_set_option(c, key, value);
-    if (key.compare(0, 4, "cof_") == 0) return yue_host::cof_set_option(c, key, value);
-    if (key.compare(0, 5, "cnet_") == 0) return yue_host::cnet_set_option(c, key, value);
-    if (key.compare(0, 4, "s2v_") == 0) return yue_host::s2v_set_option(c, key, value);
     return fail(YUE_ERR_ARG, "yue_set_option: unknown option " + key);
 }
 

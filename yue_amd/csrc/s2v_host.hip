@@ -28,27 +28,19 @@ struct yue_s2v {
     Schedule steps, pairs;
     DevBuf<int32_t> cnt;
     DevBuf<float> sim32;
-    int schedule = 1;                    // option s2v_schedule
     hipEvent_t ev[2] = {nullptr, nullptr};
-    int64_t last_ns = 0;
 };
 
 namespace {
 
-int s2v_new(yue_ctx *c) {
-    if (c->s2v) return YUE_OK;
-    HIPCHK(hipSetDevice(c->device));
-    yue_s2v *s = new yue_s2v();
-    c->s2v = s;
-    for (auto &e : s->ev) HIPCHK(hipEventCreate(&e));
-    return YUE_OK;
-}
-
 int s2v_state(yue_ctx *c, yue_s2v **out, const char *who) {
     if (!c->have_factors) return fail(YUE_ERR_ARG, std::string(who) + ": call yue_set_factors first (X, Y)");
     if (c->k > yue::kS2vMaxK) return fail(YUE_ERR_ARG, std::string(who) + ": needs k <= 128");
-    const int rc = s2v_new(c);
-    if (rc) return rc;
+    if (!c->s2v) {
+        HIPCHK(hipSetDevice(c->device));
+        c->s2v = new yue_s2v();
+        for (auto &e : c->s2v->ev) HIPCHK(hipEventCreate(&e));
+    }
     yue_s2v *s = c->s2v;
     if (s->m != c->m || s->n != c->n) {          // other factors: nothing uploaded for the old shape survives
         s->m = c->m; s->n = c->n;
@@ -92,10 +84,10 @@ int build_schedule(Schedule &s, const int32_t *a, const int32_t *b, int64_t coun
 }
 
 template <bool PAIRS>
-int run_pass(yue_ctx *c, yue_s2v *s, const Schedule &sch, yue::S2vArgs a) {
+int run_pass(yue_ctx *c, const Schedule &sch, yue::S2vArgs a) {
     if (sch.count == 0) return YUE_OK;
     a.order = sch.order.p;
-    if (s->schedule == 0) {
+    if (c->opt_s2v_schedule == 0) {
         a.begin = 0; a.count = sch.count;
         yue_host::with_kr(c->k, [&](auto kr) {
             constexpr int KR = kr() > 2 ? 2 : kr();
@@ -129,24 +121,8 @@ void s2v_release(yue_ctx *c) {
     c->s2v = nullptr;
 }
 
-int s2v_set_option(yue_ctx *c, const std::string &key, int64_t value) {
-    if (key != "s2v_schedule") return fail(YUE_ERR_ARG, "yue_set_option: unknown option " + key);
-    if (value != 0 && value != 1) return fail(YUE_ERR_ARG, "yue_set_option: s2v_schedule must be 0 (one wave walks all steps) or 1 (levels)");
-    const int rc = s2v_new(c);                       // the option may come before any upload
-    if (rc) return rc;
-    c->s2v->schedule = (int)value;
-    return YUE_OK;
-}
-
-int s2v_get_option(yue_ctx *c, const std::string &key, int64_t *value) {
-    const yue_s2v *s = c->s2v;
-    if (key == "s2v_schedule") *value = s ? s->schedule : 1;
-    else if (key == "s2v_levels_steps") *value = s ? s->steps.levels : 0;
-    else if (key == "s2v_levels_pairs") *value = s ? s->pairs.levels : 0;
-    else if (key == "s2v_last_ns") *value = s ? s->last_ns : 0;         // device time of the last yue_s2v_epoch
-    else return fail(YUE_ERR_ARG, "yue_get_option: unknown option " + key);
-    return YUE_OK;
-}
+// which: 0 the rating steps' levels, 1 the similarity pairs'
+int64_t s2v_levels(const yue_ctx *c, int which) { return !c->s2v ? 0 : which == 0 ? c->s2v->steps.levels : c->s2v->pairs.levels; }
 
 }  // namespace yue_host
 
@@ -234,14 +210,14 @@ int yue_s2v_epoch(yue_ctx *c, double lr, double regU, double regI, double regB, 
     HIPCHK(hipEventRecord(s->ev[0], c->stream));
     HIPCHK(hipMemcpyAsync(s->bu0.p, s->Bu.p, (size_t)s->m * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     a.err2 = s->err2.p;
-    if ((rc = run_pass<false>(c, s, s->steps, a))) return rc;
+    if ((rc = run_pass<false>(c, s->steps, a))) return rc;
     a.err2 = s->err2.p + T;
-    if ((rc = run_pass<true>(c, s, s->pairs, a))) return rc;
+    if ((rc = run_pass<true>(c, s->pairs, a))) return rc;
     HIPCHK(hipEventRecord(s->ev[1], c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     float ms = 0.0f;
     HIPCHK(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
-    s->last_ns = (int64_t)(1e6 * (double)ms);
+    c->s2v_ns = (int64_t)(1e6 * (double)ms);
     if (err2_steps && T > 0) HIPCHK(hipMemcpy(err2_steps, s->err2.p, (size_t)T * sizeof(double), hipMemcpyDeviceToHost));
     if (err2_pairs && Pn > 0) HIPCHK(hipMemcpy(err2_pairs, s->err2.p + T, (size_t)Pn * sizeof(double), hipMemcpyDeviceToHost));
     return YUE_OK;

@@ -9,6 +9,8 @@
 
 using yue_host::fail;
 
+static_assert(yue_host::kWrmfStageHost == yue::kWrmfStage, "the option table's lower end of wrmf_long_pairs is the kernels' stage");
+
 // Per side (0: user rows solved from Y, 1: item rows solved from X): the pairs, the longest-first schedule and the chunks
 // of the long rows.  Built once per data set by yue_wrmf_set_pairs.
 struct yue_wrmf_side {
@@ -25,8 +27,6 @@ struct yue_wrmf {
     DevBuf<double> gram_part, G, ws, row_loss, loss;
     DevBuf<int> status;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    int64_t last_ns = 0, last_long_ns = 0;
-    int64_t long_pairs = 2048;       // rows with more pairs are summed by several workgroups (chunks of this many pairs) before their solve
 };
 
 namespace yue_host {
@@ -145,27 +145,7 @@ int wrmf_gram(yue_ctx *c, int side, const double **G) {
     return YUE_OK;
 }
 
-int wrmf_set_option(yue_ctx *c, const std::string &key, int64_t value) {
-    if (key == "wrmf_long_pairs") {
-        if (value < yue::kWrmfStage) return fail(YUE_ERR_ARG, "yue_set_option: wrmf_long_pairs must be >= 32");
-        yue_wrmf *w = nullptr;
-        int rc = wrmf_state(c, &w);
-        if (rc) return rc;
-        w->long_pairs = value;       // takes effect at the next yue_wrmf_set_pairs
-        return YUE_OK;
-    }
-    return fail(YUE_ERR_ARG, "yue_set_option: unknown option " + key);
-}
-
-int wrmf_get_option(yue_ctx *c, const std::string &key, int64_t *value) {
-    const yue_wrmf *w = c->wrmf;
-    if (key == "wrmf_long_pairs") *value = w ? w->long_pairs : 2048;
-    else if (key == "wrmf_last_ns") *value = w ? w->last_ns : 0;                  // device time of the last half-sweep
-    else if (key == "wrmf_last_long_ns") *value = w ? w->last_long_ns : 0;        // ... of its long-row chunks
-    else if (key == "wrmf_long_rows_user" || key == "wrmf_long_rows_item") *value = w ? w->side[key.back() == 'm' ? 1 : 0].n_long : 0;
-    else return fail(YUE_ERR_ARG, "yue_get_option: unknown option " + key);
-    return YUE_OK;
-}
+int64_t wrmf_long_rows(const yue_ctx *c, int side) { return c->wrmf ? c->wrmf->side[side].n_long : 0; }
 
 }  // namespace yue_host
 
@@ -193,8 +173,8 @@ int yue_wrmf_set_pairs(yue_ctx *c, const int64_t *u_ptr, const int32_t *u_items,
     yue_wrmf *w = nullptr;
     if ((rc = wrmf_state(c, &w))) return rc;
     w->m = 0;                                                  // invalid until both sides are up
-    if ((rc = upload_side(w->long_pairs, w->side[0], u_ptr, u_items, u_counts, m, nnz))) return rc;
-    if ((rc = upload_side(w->long_pairs, w->side[1], i_ptr, i_users, i_counts, n, nnz))) return rc;
+    if ((rc = upload_side(c->opt_wrmf_long_pairs, w->side[0], u_ptr, u_items, u_counts, m, nnz))) return rc;
+    if ((rc = upload_side(c->opt_wrmf_long_pairs, w->side[1], i_ptr, i_users, i_counts, n, nnz))) return rc;
     const int64_t chunks = std::max(w->side[0].chunks, w->side[1].chunks);
     HIPCHK(w->gram_part.resize((size_t)yue::kWrmfGramBlocks * yue::kWrmfWsStride));
     HIPCHK(w->G.resize((size_t)yue::kWrmfSlots * yue::kWrmfThreads));
@@ -249,8 +229,8 @@ int yue_wrmf_half_sweep(yue_ctx *c, int side, double alpha, double reg, double *
     float ms_all = 0.0f, ms_long = 0.0f;
     HIPCHK(hipEventElapsedTime(&ms_all, w->ev[0], w->ev[3]));
     HIPCHK(hipEventElapsedTime(&ms_long, w->ev[1], w->ev[2]));
-    w->last_ns = (int64_t)(1e6 * (double)ms_all);
-    w->last_long_ns = (int64_t)(1e6 * (double)ms_long);
+    c->wrmf_ns[0] = (int64_t)(1e6 * (double)ms_all);
+    c->wrmf_ns[1] = (int64_t)(1e6 * (double)ms_long);
     if (status != INT_MAX)
         return fail(YUE_ERR_ARG, std::string("yue_wrmf_half_sweep: non-positive pivot in the Cholesky factorisation of ") + (side == 0 ? "user" : "item") +
                                      " row " + std::to_string(status) + " (A = F^T F + C + reg*I is not positive definite: raise reg)");
