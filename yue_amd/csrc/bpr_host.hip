@@ -295,8 +295,7 @@ int run_rounds(yue_ctx *c, yue::TrainArgs a, const std::vector<int64_t> &bounds,
             HIPCHK(bigger.resize(need));
             HIPCHK(hipMemcpyAsync(bigger.p, c->Q.p, (size_t)c->n * c->k * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
             HIPCHK(hipStreamSynchronize(c->stream));
-            c->Q.release();
-            c->Q = bigger;
+            c->Q = std::move(bigger);
             a.Q = c->Q.p;
         }
         if (!meta) {
@@ -318,14 +317,11 @@ int run_rounds(yue_ctx *c, yue::TrainArgs a, const std::vector<int64_t> &bounds,
     const bool timed = c->timing_stride > 0 && !ne.empty();
     if (timed) {
         if (c->ev_used == c->ev_pool.size()) {
-            hipEvent_t s, t;
-            HIPCHK(hipEventCreate(&s));
-            HIPCHK(hipEventCreate(&t));
-            c->ev_pool.emplace_back(s, t);
+            c->ev_pool.emplace_back();
             c->ev_triplets.push_back(0);
             c->ev_launches.push_back(0);
         }
-        HIPCHK(hipEventRecord(c->ev_pool[c->ev_used].first, c->stream));
+        HIPCHK(c->ev_pool[c->ev_used].first.record(c->stream));
     }
     size_t pos = 0;
     for (int64_t r = 0; r < R; ++r) {
@@ -342,7 +338,7 @@ int run_rounds(yue_ctx *c, yue::TrainArgs a, const std::vector<int64_t> &bounds,
         if ((rc = after_round(r))) return rc;
     }
     if (timed) {
-        HIPCHK(hipEventRecord(c->ev_pool[c->ev_used].second, c->stream));
+        HIPCHK(c->ev_pool[c->ev_used].second.record(c->stream));
         c->ev_triplets[c->ev_used] = bounds.back() - bounds.front();
         c->ev_launches[c->ev_used] = (int64_t)ne.size();
         c->ev_used++;
@@ -713,10 +709,10 @@ int yue_bpr_epoch(yue_ctx *c, uint64_t seed, uint32_t epoch, int64_t round_event
     if ((rc = sumsq_async(c, psq_done ? c->psq_slots.p : nullptr))) return rc;
     if ((rc = read_scalars(c, nll_out, sumsqP_out, sumsqQ_out))) return rc;
     if (yue_host::on_communicator(c)) {
-        float ms = 0.f;
+        double ms = 0.0;
         HIPCHK(hipEventSynchronize(c->ev_t_comm));
-        HIPCHK(hipEventElapsedTime(&ms, c->ev_t_rounds, c->ev_t_comm));
-        c->comm_wait_ms = ms > 0.f ? ms : 0.0;
+        HIPCHK(yue_host::elapsed(c->ev_t_rounds, c->ev_t_comm, &ms));
+        c->comm_wait_ms = ms > 0.0 ? ms : 0.0;
     }
     return YUE_OK;
 }
@@ -759,8 +755,8 @@ int yue_get_kernel_timing(yue_ctx *c, double *total_ms, int64_t *launches, int64
     double tot = 0.0;
     int64_t trip = 0, nl = 0;
     for (size_t t = 0; t < c->ev_used; ++t) {
-        float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, c->ev_pool[t].first, c->ev_pool[t].second));
+        double ms = 0.0;
+        HIPCHK(yue_host::elapsed(c->ev_pool[t].first, c->ev_pool[t].second, &ms));
         tot += ms;
         trip += c->ev_triplets[t];
         nl += c->ev_launches[t];

@@ -10,7 +10,8 @@
 
 #include <limits>
 
-using gcn::upload;
+using yue_host::download;
+using yue_host::upload;
 using yue_host::fail;
 
 namespace {
@@ -91,19 +92,12 @@ int64_t var_count(const yue_cdae *s, int v) {
 
 unsigned dense_blocks(int64_t count) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(8192, (count + 255) / 256)); }
 
-int cdae_new(yue_ctx *c) {
-    if (c->cdae) return YUE_OK;
-    HIPCHK(hipSetDevice(c->device));
-    c->cdae = new yue_cdae();
-    return YUE_OK;
-}
-
 int stamp(yue_ctx *c, yue_cdae *s, int phase) { return gcn::stamp(c, s->timer, phase); }
 
 int cdae_ready(yue_ctx *c, yue_cdae **out, const char *who) {
     const std::string w(who);
     if (!c) return fail(YUE_ERR_ARG, w + ": null context");
-    yue_cdae *s = c->cdae;
+    yue_cdae *s = c->cdae.get();
     if (!s || !s->have_data) return fail(YUE_ERR_ARG, w + ": call yue_cdae_set_data first");
     if (!s->have_params) return fail(YUE_ERR_ARG, w + ": call yue_cdae_set_params first");
     HIPCHK(hipSetDevice(c->device));
@@ -371,29 +365,7 @@ int finish(yue_ctx *c, yue_cdae *s) {
     return gcn::read_times(s->timer, c->cdae_ns, kPhases);
 }
 
-template <typename T>
-int download(T *dst, const DevBuf<T> &src, size_t count) {
-    if (dst && count) HIPCHK(hipMemcpy(dst, src.p, count * sizeof(T), hipMemcpyDeviceToHost));
-    return YUE_OK;
-}
-
 }  // namespace
-
-namespace yue_host {
-
-void cdae_release(yue_ctx *c) {
-    yue_cdae *s = c->cdae;
-    if (!s) return;
-    s->uptr.release(); s->uitems.release(); s->ucnt.release(); s->imap.release(); s->umap.release();
-    for (int v = 0; v < kVars; ++v) { s->var[v].release(); s->mom[v].release(); s->vel[v].release(); }
-    s->idx.release(); s->xw.release(); s->hid.release(); s->dz.release(); s->logit.release(); s->ypred.release(); s->e.release();
-    s->partial.release(); s->partial_b.release(); s->gWd.release(); s->gBd.release(); s->gWe.release(); s->gU.release(); s->gB.release();
-    s->usq.release(); s->loss.release(); s->sq.release(); s->sat.release(); s->timer.release();
-    delete s;
-    c->cdae = nullptr;
-}
-
-}  // namespace yue_host
 
 extern "C" {
 
@@ -413,8 +385,8 @@ int yue_cdae_set_data(yue_ctx *c, int64_t m, int64_t n, const int64_t *ptr, cons
             if (counts[p] < 1 || counts[p] >= (1 << 24)) return fail(YUE_ERR_ARG, "yue_cdae_set_data: user " + std::to_string(u) + ": a count must be 1 .. 2^24 - 1");
         }
     int rc;
-    if ((rc = cdae_new(c))) return rc;
-    yue_cdae *s = c->cdae;
+    yue_cdae *s = nullptr;
+    if ((rc = yue_host::state(c, c->cdae, &s))) return rc;
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
     s->have_data = false;
@@ -432,7 +404,7 @@ int yue_cdae_set_data(yue_ctx *c, int64_t m, int64_t n, const int64_t *ptr, cons
 int yue_cdae_set_params(yue_ctx *c, int h, const float *U, const float *W, const float *Wd, const float *b, const float *bd) {
     if (!c || !U || !W || !Wd || !b || !bd) return fail(YUE_ERR_ARG, "yue_cdae_set_params: null argument");
     if (h < 1 || h > yue::kCdaeMaxH) return fail(YUE_ERR_ARG, "yue_cdae_set_params: needs 1 <= h <= 128");
-    yue_cdae *s = c->cdae;
+    yue_cdae *s = c->cdae.get();
     if (!s || !s->have_data) return fail(YUE_ERR_ARG, "yue_cdae_set_params: call yue_cdae_set_data first (m, n)");
     const int64_t m = s->m, n = s->n;
     const float *given[kVars] = {U, W, Wd, b, bd};
@@ -462,7 +434,7 @@ int yue_cdae_set_params(yue_ctx *c, int h, const float *U, const float *W, const
 // every pointer may be NULL; params, m_out and v_out each hold the five arrays in the order U, W, W' [h][n], b, b'
 int yue_cdae_get_params(yue_ctx *c, float *const *params, float *const *m_out, float *const *v_out) {
     if (!c || !c->cdae || !c->cdae->have_params) return fail(YUE_ERR_ARG, "yue_cdae_get_params: call yue_cdae_set_params first");
-    yue_cdae *s = c->cdae;
+    yue_cdae *s = c->cdae.get();
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
     const int64_t n = s->n, h = s->h;

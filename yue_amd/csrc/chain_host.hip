@@ -99,12 +99,11 @@ int chain_launch(yue_ctx *c, const int32_t *ev_u, const int32_t *ev_i, const int
         block = dim3((unsigned)threads);
         // (one XCD: a workgroup in eight stays, and the XCD has an eighth of the CUs -- the same grid size for per_cu per CU of it)
         grid = dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((int64_t)per_cu * cus, one_xcd ? (int64_t)per_cu * cus : (R + runs_per_block - 1) / runs_per_block)));
-        HIPCHK(hipEventRecord(c->ev_chain0, c->stream));
+        HIPCHK(c->ev_chain0.record(c->stream));
         hipLaunchKernelGGL(kernel, grid, block, 0, c->stream, a, ev_i, ev_j, c->ch_ord_i.p, c->ch_ord_j.p);
-        HIPCHK(hipEventRecord(c->ev_chain1, c->stream));
+        HIPCHK(c->ev_chain1.record(c->stream));
         return YUE_OK;
     };
-    if (!c->ev_chain0) { HIPCHK(hipEventCreate(&c->ev_chain0)); HIPCHK(hipEventCreate(&c->ev_chain1)); }
     a.xcd = 0u; a.groups = c->ch_ctl.p + 3;
     // ring of 8 prefetched triplets per wave (k_bpr_chain at k > 128: 4, register budget)
 #define YUE_CHAIN3(KR_, PV_, G_, X_) (c->opt_chain_fast ? launch(yue::k_bpr_chain3<KR_, PV_, G_, true, X_>, 320, 1) : launch(yue::k_bpr_chain3<KR_, PV_, G_, false, X_>, 320, 1))
@@ -157,7 +156,7 @@ int chain_launch(yue_ctx *c, const int32_t *ev_u, const int32_t *ev_i, const int
     }
 #endif
     c->chain_runs = R; c->chain_waves = (one_xcd ? c->chain_groups : blocks) * waves_per_block;
-    { float ms = 0.0f; HIPCHK(hipEventElapsedTime(&ms, c->ev_chain0, c->ev_chain1)); c->chain_kernel_us = (int64_t)(1e3 * ms); }
+    { double ms = 0.0; HIPCHK(yue_host::elapsed(c->ev_chain0, c->ev_chain1, &ms)); c->chain_kernel_us = (int64_t)(1e3 * ms); }
     if (st) return fail(YUE_ERR_HIP, std::string("exact path: a wave gave up waiting for a row (") + ((st & 2u) ? "a row's version ran past a waiting touch" : "spin limit") +
                                     "): internal error, the factors on the device are not usable");
     return YUE_OK;

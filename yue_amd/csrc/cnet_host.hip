@@ -8,6 +8,7 @@
 #include <numeric>
 
 using yue_host::fail;
+using yue_host::upload;
 
 struct yue_cnet {
     int64_t m = 0, n = 0, nnz = 0;               // pairs (m == 0: none)
@@ -33,40 +34,12 @@ struct yue_cnet {
     DevBuf<int> flag0, flag1;
     DevBuf<uint64_t> keep, cum;
     DevBuf<double> norm, sims;
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    Event ev[2];
 };
-
-namespace yue_host {
-
-void cnet_release(yue_ctx *c) {
-    yue_cnet *k = c->cnet;
-    if (!k) return;
-    k->u_ptr.release(); k->i_ptr.release(); k->pref.release(); k->total.release(); k->dest.release(); k->u_items.release(); k->i_users.release();
-    k->walks.release(); k->cnt.release(); k->list.release(); k->list_n.release(); k->net.release(); k->friends.release();
-    k->seg_len.release(); k->seg_pre.release();
-    k->syn0.release(); k->syn1.release(); k->acc0.release(); k->acc1.release(); k->flag0.release(); k->flag1.release();
-    k->keep.release(); k->cum.release(); k->norm.release(); k->sims.release();
-    for (auto &e : k->ev) if (e) (void)hipEventDestroy(e);
-    delete k;
-    c->cnet = nullptr;
-}
-
-}  // namespace yue_host
 
 namespace {
 
 constexpr int kDefaultRoundWalks = 64;       // chosen by the planted-groups quality test
-
-int cnet_state(yue_ctx *c, yue_cnet **out) {
-    if (!c->cnet) {
-        HIPCHK(hipSetDevice(c->device));
-        yue_cnet *k = new yue_cnet();
-        c->cnet = k;
-        for (auto &e : k->ev) HIPCHK(hipEventCreate(&e));
-    }
-    *out = c->cnet;
-    return YUE_OK;
-}
 
 // ptr[rows + 1] from 0 to nnz, ids sorted-unique in [0, bound)
 int check_csr(const int64_t *ptr, const int32_t *ids, int64_t rows, int64_t bound, int64_t nnz, const char *what) {
@@ -82,19 +55,10 @@ int check_csr(const int64_t *ptr, const int32_t *ids, int64_t rows, int64_t boun
     return YUE_OK;
 }
 
-template <typename T>
-int upload(DevBuf<T> &buf, const T *src, int64_t count) {
-    HIPCHK(buf.resize((size_t)std::max<int64_t>(count, 1)));
-    if (count > 0) HIPCHK(hipMemcpy(buf.p, src, (size_t)count * sizeof(T), hipMemcpyHostToDevice));
-    return YUE_OK;
-}
-
 int stop_clock(yue_ctx *c, yue_cnet *k) {
-    HIPCHK(hipEventRecord(k->ev[1], c->stream));
+    HIPCHK(k->ev[1].record(c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    float ms = 0.0f;
-    HIPCHK(hipEventElapsedTime(&ms, k->ev[0], k->ev[1]));
-    c->cnet_ns = (int64_t)(1e6 * (double)ms);
+    HIPCHK(yue_host::elapsed(k->ev[0], k->ev[1], &c->cnet_ns));
     return YUE_OK;
 }
 
@@ -124,7 +88,7 @@ int yue_cnet_set_pairs(yue_ctx *c, int64_t m, int64_t n, const int64_t *u_ptr, c
     }
     HIPCHK(hipSetDevice(c->device));
     yue_cnet *k = nullptr;
-    if ((rc = cnet_state(c, &k))) return rc;
+    if ((rc = yue_host::state(c, c->cnet, &k))) return rc;
     k->m = 0;
     if ((rc = upload(k->u_ptr, u_ptr, m + 1)) || (rc = upload(k->u_items, u_items, nnz)) || (rc = upload(k->i_ptr, i_ptr, n + 1)) ||
         (rc = upload(k->i_users, i_users, nnz)))
@@ -147,7 +111,7 @@ int yue_cnet_set_pairs(yue_ctx *c, int64_t m, int64_t n, const int64_t *u_ptr, c
 
 int yue_cnet_walks(yue_ctx *c, int T, int L, uint64_t seed, int32_t *walks_out, int64_t *nw_out) {
     if (!c || !nw_out) return fail(YUE_ERR_ARG, "yue_cnet_walks: null argument");
-    yue_cnet *k = c->cnet;
+    yue_cnet *k = c->cnet.get();
     if (!k || k->m == 0) return fail(YUE_ERR_ARG, "yue_cnet_walks: call yue_cnet_set_pairs first");
     if (T < 1 || L < 2 || L > yue::kCnetMaxL || (int64_t)T * (L - 1) > yue::kCnetMaxVisited)
         return fail(YUE_ERR_ARG, "yue_cnet_walks: need T >= 1, 2 <= L <= 64 and T (L - 1) <= 15360 (visited[start] lives in LDS)");
@@ -170,7 +134,7 @@ int yue_cnet_walks(yue_ctx *c, int T, int L, uint64_t seed, int32_t *walks_out, 
     yue::CnetArgs a{};
     a.m = k->m; a.n = k->n; a.u_ptr = k->u_ptr.p; a.u_items = k->u_items.p; a.i_ptr = k->i_ptr.p; a.i_users = k->i_users.p;
     a.pref = k->pref.p; a.total = k->total.p; a.net = k->net.p; a.dest = k->dest.p; a.walks = k->walks.p; a.T = T; a.L = L; a.seed = seed;
-    HIPCHK(hipEventRecord(k->ev[0], c->stream));
+    HIPCHK(k->ev[0].record(c->stream));
     hipLaunchKernelGGL(yue::k_cnet_walk, dim3((unsigned)nnet), dim3(64), (size_t)T * (L - 1) * sizeof(int32_t), c->stream, a);
     HIPCHK(hipGetLastError());
     if ((rc = stop_clock(c, k))) return rc;
@@ -187,7 +151,7 @@ int yue_cnet_set_walks(yue_ctx *c, int64_t m, int64_t nw, int L, const int32_t *
         if (walks[e] < 0 || walks[e] >= m) return fail(YUE_ERR_ARG, "yue_cnet_set_walks: user id out of range");
     HIPCHK(hipSetDevice(c->device));
     yue_cnet *k = nullptr;
-    int rc = cnet_state(c, &k);
+    int rc = yue_host::state(c, c->cnet, &k);
     if (rc) return rc;
     new_walks(k, m, 0, L);
     if ((rc = upload(k->walks, walks, nw * L))) return rc;
@@ -205,7 +169,7 @@ int yue_cnet_set_sentences(yue_ctx *c, int64_t m, int64_t ns, const int64_t *ptr
         if (ids[e] < 0 || ids[e] >= m) return fail(YUE_ERR_ARG, "yue_cnet_set_sentences: id out of range");
     HIPCHK(hipSetDevice(c->device));
     yue_cnet *k = nullptr;
-    int rc = cnet_state(c, &k);
+    int rc = yue_host::state(c, c->cnet, &k);
     if (rc) return rc;
     new_walks(k, m, 0, 0);
     k->s_ptr.assign(ptr, ptr + ns + 1);
@@ -216,7 +180,7 @@ int yue_cnet_set_sentences(yue_ctx *c, int64_t m, int64_t ns, const int64_t *ptr
 
 int yue_cnet_embed(yue_ctx *c, int dim, int window, int epochs, int negative, int64_t round_walks, uint64_t seed, float *W_out) {
     if (!c) return fail(YUE_ERR_ARG, "yue_cnet_embed: null context");
-    yue_cnet *k = c->cnet;
+    yue_cnet *k = c->cnet.get();
     if (!k || (k->nw == 0 && !k->sent)) return fail(YUE_ERR_ARG, "yue_cnet_embed: call yue_cnet_walks or yue_cnet_set_walks first (or yue_cnet_set_sentences)");
     if (dim < 1 || dim > yue::kCnetMaxDim || window < 1 || epochs < 1 || negative < 0 || negative > 64 || round_walks < 0)
         return fail(YUE_ERR_ARG, "yue_cnet_embed: need 1 <= dim <= 128, window >= 1, epochs >= 1, 0 <= negative <= 64, round_walks >= 0");
@@ -305,7 +269,7 @@ int yue_cnet_embed(yue_ctx *c, int dim, int window, int epochs, int negative, in
     a.list = k->list.p; a.list_n = k->list_n.p;
     if (sent) { a.len = k->seg_len.p; a.wpre = k->seg_pre.p; a.words = words; }
     a.L = L; a.dim = dim; a.window = window; a.negative = negative; a.epochs = epochs; a.seed = seed;
-    HIPCHK(hipEventRecord(k->ev[0], c->stream));
+    HIPCHK(k->ev[0].record(c->stream));
     hipLaunchKernelGGL(yue::k_cnet_embed_init, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, c->stream, a);
     HIPCHK(hipGetLastError());
     for (int ep = 0; ep < epochs; ++ep)
@@ -342,7 +306,7 @@ int yue_cnet_set_embedding(yue_ctx *c, int64_t m, int dim, const float *W, const
     }
     HIPCHK(hipSetDevice(c->device));
     yue_cnet *k = nullptr;
-    int rc = cnet_state(c, &k);
+    int rc = yue_host::state(c, c->cnet, &k);
     if (rc) return rc;
     k->em = 0;
     if ((rc = upload(k->syn0, W, m * dim)) || (rc = upload(k->net, net.data(), (int64_t)net.size()))) return rc;
@@ -352,7 +316,7 @@ int yue_cnet_set_embedding(yue_ctx *c, int64_t m, int dim, const float *W, const
 
 int yue_cnet_friends(yue_ctx *c, int K, int32_t *friends_out, double *sims_out) {
     if (!c) return fail(YUE_ERR_ARG, "yue_cnet_friends: null context");
-    yue_cnet *k = c->cnet;
+    yue_cnet *k = c->cnet.get();
     if (!k || k->em == 0) return fail(YUE_ERR_ARG, "yue_cnet_friends: call yue_cnet_embed or yue_cnet_set_embedding first");
     if (K < 1 || K > yue::kCnetMaxK) return fail(YUE_ERR_ARG, "yue_cnet_friends: K = " + std::to_string(K) + " is not supported (1 <= K <= 100)");
     HIPCHK(hipSetDevice(c->device));
@@ -362,7 +326,7 @@ int yue_cnet_friends(yue_ctx *c, int K, int32_t *friends_out, double *sims_out) 
     yue::CnetFriendsArgs a{};
     a.m = m; a.nnet = k->nnet; a.net = k->net.p; a.W = k->syn0.p; a.norm = k->norm.p; a.dim = k->dim; a.K = K;
     a.friends = k->friends.p; a.sims = k->sims.p;
-    HIPCHK(hipEventRecord(k->ev[0], c->stream));
+    HIPCHK(k->ev[0].record(c->stream));
     hipLaunchKernelGGL(yue::k_cnet_norms, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, c->stream, a);
     if (k->nnet > 0)
         hipLaunchKernelGGL(yue::k_cnet_friends, dim3((unsigned)((k->nnet + yue::kCnetFrQ - 1) / yue::kCnetFrQ)), dim3(yue::kCnetFrThreads), 0, c->stream, a);

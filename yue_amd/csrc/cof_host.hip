@@ -9,6 +9,7 @@
 #include <numeric>
 
 using yue_host::fail;
+using yue_host::upload;
 
 static_assert(yue_host::kCofRangeHost == yue::kCofRange, "the option table's upper end of cof_pass_items is the count kernel's range");
 
@@ -36,46 +37,11 @@ struct yue_cof {
     int64_t st_n = -1;
     int st_k = 0;
     DevBuf<int> status;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    std::vector<hipEvent_t> lev_ev;  // one in front of every level's launch and one behind the last
+    Event ev[2];
+    std::vector<Event> lev_ev;       // one in front of every level's launch and one behind the last
 };
 
-namespace yue_host {
-
-void cof_release(yue_ctx *c) {
-    yue_cof *x = c->cof;
-    if (!x) return;
-    x->co_ptr.release(); x->row_nnz.release(); x->cursor.release(); x->co_idx.release(); x->co_cnt.release(); x->events.release();
-    x->sp_ptr.release(); x->sp_idx.release(); x->sp_val.release();
-    x->sched.release(); x->lpos.release(); x->cptr.release(); x->cbeg.release(); x->cend.release(); x->ws.release();
-    x->G.release(); x->w.release(); x->c.release(); x->status.release();
-    for (auto &e : x->ev) if (e) (void)hipEventDestroy(e);
-    for (auto &e : x->lev_ev) (void)hipEventDestroy(e);
-    delete x;
-    c->cof = nullptr;
-}
-
-}  // namespace yue_host
-
 namespace {
-
-int cof_state(yue_ctx *c, yue_cof **out) {
-    if (!c->cof) {
-        HIPCHK(hipSetDevice(c->device));
-        yue_cof *x = new yue_cof();
-        c->cof = x;
-        for (auto &e : x->ev) HIPCHK(hipEventCreate(&e));
-    }
-    *out = c->cof;
-    return YUE_OK;
-}
-
-template <typename T>
-int upload(DevBuf<T> &b, const std::vector<T> &h) {
-    HIPCHK(b.resize(std::max<size_t>(h.size(), 1)));
-    if (!h.empty()) HIPCHK(hipMemcpy(b.p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-    return YUE_OK;
-}
 
 // The rows level by level (inside a level: most pairs first, ties by id) and the chunks of the rows with more than long_pairs
 // pairs; rebuilt when the pairs (a new yue_wrmf_set_pairs), the SPPMI or wrmf_long_pairs changed.
@@ -137,7 +103,7 @@ int yue_cof_cooccur(yue_ctx *c, int filter, int64_t *nnz_out) {
     if (!yue_host::wrmf_pairs_view(c, 0, &vu) || !yue_host::wrmf_pairs_view(c, 1, &vi))
         return fail(YUE_ERR_ARG, "yue_cof_cooccur: call yue_wrmf_set_pairs first (after yue_set_factors)");
     yue_cof *x = nullptr;
-    int rc = cof_state(c, &x);
+    int rc = yue_host::state(c, c->cof, &x);
     if (rc) return rc;
     HIPCHK(hipSetDevice(c->device));
     const int64_t n = c->n;
@@ -152,7 +118,7 @@ int yue_cof_cooccur(yue_ctx *c, int filter, int64_t *nnz_out) {
     a.n = n; a.u_ptr = vu.ptr; a.u_items = vu.idx; a.i_ptr = vi.ptr; a.i_users = vi.idx; a.i_counts = vi.cnt;
     a.cursor = x->cursor.p; a.events = x->events.p; a.filter = filter; a.range = (int)c->opt_cof_pass_items;
     a.row_nnz = x->row_nnz.p; a.fill = 0;
-    HIPCHK(hipEventRecord(x->ev[0], c->stream));
+    HIPCHK(x->ev[0].record(c->stream));
     hipLaunchKernelGGL(yue::k_cof_events, dim3((unsigned)((n + yue::kCofThreads - 1) / yue::kCofThreads)), dim3(yue::kCofThreads), 0, c->stream, a);
     hipLaunchKernelGGL(yue::k_cof_cooccur, dim3((unsigned)n), dim3(yue::kCofThreads), 0, c->stream, a);
     HIPCHK(hipGetLastError());
@@ -170,11 +136,9 @@ int yue_cof_cooccur(yue_ctx *c, int filter, int64_t *nnz_out) {
     a.fill = 1; a.ptr = x->co_ptr.p; a.idx = x->co_idx.p; a.cnt = x->co_cnt.p;
     hipLaunchKernelGGL(yue::k_cof_cooccur, dim3((unsigned)n), dim3(yue::kCofThreads), 0, c->stream, a);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(x->ev[1], c->stream));
+    HIPCHK(x->ev[1].record(c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    float ms = 0.0f;
-    HIPCHK(hipEventElapsedTime(&ms, x->ev[0], x->ev[1]));
-    c->cof_ns[0] = (int64_t)(1e6 * (double)ms);
+    HIPCHK(yue_host::elapsed(x->ev[0], x->ev[1], &c->cof_ns[0]));
     x->co_n = n;
     x->co_nnz = nnz;
     if (nnz_out) *nnz_out = nnz;
@@ -183,7 +147,7 @@ int yue_cof_cooccur(yue_ctx *c, int filter, int64_t *nnz_out) {
 
 int yue_cof_get_cooccur(yue_ctx *c, int64_t *ptr, int32_t *idx, int32_t *cnt) {
     if (!c || !c->cof || c->cof->co_n < 0) return fail(YUE_ERR_ARG, "yue_cof_get_cooccur: call yue_cof_cooccur first");
-    yue_cof *x = c->cof;
+    yue_cof *x = c->cof.get();
     if (!ptr || (x->co_nnz > 0 && (!idx || !cnt))) return fail(YUE_ERR_ARG, "yue_cof_get_cooccur: null output array");
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipMemcpy(ptr, x->co_ptr.p, ((size_t)x->co_n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
@@ -217,7 +181,7 @@ int yue_cof_set_sppmi(yue_ctx *c, const int64_t *ptr, const int32_t *idx, const 
                 return fail(YUE_ERR_ARG, "yue_cof_set_sppmi: not symmetric at (" + std::to_string(i) + ", " + std::to_string(j) + ")");
         }
     yue_cof *x = nullptr;
-    int rc = cof_state(c, &x);
+    int rc = yue_host::state(c, c->cof, &x);
     if (rc) return rc;
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -250,7 +214,7 @@ int yue_cof_set_state(yue_ctx *c, const double *G, const double *w, const double
     if (!c || !c->have_factors) return fail(YUE_ERR_ARG, "yue_cof_set_state: call yue_set_factors first (n, k)");
     if (!G || !w || !cb) return fail(YUE_ERR_ARG, "yue_cof_set_state: null array");
     yue_cof *x = nullptr;
-    int rc = cof_state(c, &x);
+    int rc = yue_host::state(c, c->cof, &x);
     if (rc) return rc;
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -268,7 +232,7 @@ int yue_cof_set_state(yue_ctx *c, const double *G, const double *w, const double
 int yue_cof_get_state(yue_ctx *c, double *G, double *w, double *cb) {
     if (!c || !c->cof || c->cof->st_n < 0) return fail(YUE_ERR_ARG, "yue_cof_get_state: call yue_cof_set_state first");
     if (!G || !w || !cb) return fail(YUE_ERR_ARG, "yue_cof_get_state: null array");
-    yue_cof *x = c->cof;
+    yue_cof *x = c->cof.get();
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
     const size_t n = (size_t)x->st_n, k = (size_t)x->st_k;
@@ -286,7 +250,7 @@ int yue_cof_item_sweep(yue_ctx *c, double alpha, double regU, double regR) {
         return fail(YUE_ERR_ARG, "yue_cof_item_sweep: alpha, regU and regR must be finite, alpha >= 0");
     yue_host::WrmfPairsView v;
     if (!yue_host::wrmf_pairs_view(c, 1, &v)) return fail(YUE_ERR_ARG, "yue_cof_item_sweep: call yue_wrmf_set_pairs first (after yue_set_factors)");
-    yue_cof *x = c->cof;
+    yue_cof *x = c->cof.get();
     if (!x || x->sp_n != c->n) return fail(YUE_ERR_ARG, "yue_cof_item_sweep: call yue_cof_set_sppmi first (after yue_set_factors)");
     if (x->st_n != c->n || x->st_k != c->k) return fail(YUE_ERR_ARG, "yue_cof_item_sweep: call yue_cof_set_state first (G, w, c for the current n and k)");
     HIPCHK(hipSetDevice(c->device));
@@ -305,39 +269,33 @@ int yue_cof_item_sweep(yue_ctx *c, double alpha, double regU, double regR) {
     a.w.status = x->status.p;
     const int none = INT_MAX;
     HIPCHK(hipMemcpyAsync(x->status.p, &none, sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipEventRecord(x->ev[0], c->stream));
+    HIPCHK(x->ev[0].record(c->stream));
     if ((rc = yue_host::wrmf_gram(c, 1, &a.w.G))) return rc;           // X^T X, rounded to fp32 once
     if (x->chunks > 0) hipLaunchKernelGGL(yue::k_cof_chunk, dim3((unsigned)x->chunks), dim3(yue::kWrmfThreads), 0, c->stream, a);
     const int lds = yue::wrmf_dyn_lds(k);
     HIPCHK(hipFuncSetAttribute((const void *)yue::k_cof_solve, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     const bool timed = c->opt_cof_level_timing != 0;
-    while (timed && (int64_t)x->lev_ev.size() < x->levels + 1) {
-        hipEvent_t e;
-        HIPCHK(hipEventCreate(&e));
-        x->lev_ev.push_back(e);
-    }
+    if (timed && (int64_t)x->lev_ev.size() < x->levels + 1) x->lev_ev.resize((size_t)x->levels + 1);
     for (int64_t l = 0; l < x->levels; ++l) {                          // one launch per level: the stream orders the levels
         const int64_t rows = x->level_ptr[(size_t)l + 1] - x->level_ptr[(size_t)l];
         a.pos0 = x->level_ptr[(size_t)l];
-        if (timed) HIPCHK(hipEventRecord(x->lev_ev[(size_t)l], c->stream));
+        if (timed) HIPCHK(x->lev_ev[(size_t)l].record(c->stream));
         hipLaunchKernelGGL(yue::k_cof_solve, dim3((unsigned)rows), dim3(yue::kWrmfThreads), lds, c->stream, a);
     }
-    if (timed) HIPCHK(hipEventRecord(x->lev_ev[(size_t)x->levels], c->stream));
+    if (timed) HIPCHK(x->lev_ev[(size_t)x->levels].record(c->stream));
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(x->ev[1], c->stream));
+    HIPCHK(x->ev[1].record(c->stream));
     int status = INT_MAX;
     HIPCHK(hipMemcpyAsync(&status, x->status.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    float ms = 0.0f;
-    HIPCHK(hipEventElapsedTime(&ms, x->ev[0], x->ev[1]));
-    c->cof_ns[0] = (int64_t)(1e6 * (double)ms);
-    double small_ms = 0.0;
+    HIPCHK(yue_host::elapsed(x->ev[0], x->ev[1], &c->cof_ns[0]));
+    double small_ms = 0.0, ms = 0.0;
     for (int64_t l = 0; timed && l < x->levels; ++l)
         if (x->level_ptr[(size_t)l + 1] - x->level_ptr[(size_t)l] < 256) {
-            HIPCHK(hipEventElapsedTime(&ms, x->lev_ev[(size_t)l], x->lev_ev[(size_t)l + 1]));
-            small_ms += (double)ms;
+            HIPCHK(yue_host::elapsed(x->lev_ev[(size_t)l], x->lev_ev[(size_t)l + 1], &ms));
+            small_ms += ms;
         }
-    c->cof_ns[1] = (int64_t)(1e6 * small_ms);
+    c->cof_ns[1] = yue_host::ns_of(small_ms);
     if (status != INT_MAX)
         return fail(YUE_ERR_ARG, "yue_cof_item_sweep: non-positive pivot in a Cholesky factorisation of item row " + std::to_string(status) +
                                      " (raise regU or regR)");

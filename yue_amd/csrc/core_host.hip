@@ -25,12 +25,12 @@ int yue_ctx_create(int device, yue_ctx **out) {
     const auto init = [c]() -> int {
         HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
         HIPCHK(hipStreamCreateWithFlags(&c->comm_stream, hipStreamNonBlocking));
-        HIPCHK(hipEventCreateWithFlags(&c->ev_rounds, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&c->ev_comm, hipEventDisableTiming));
-        HIPCHK(hipEventCreate(&c->ev_t_rounds));
-        HIPCHK(hipEventCreate(&c->ev_t_comm));
-        HIPCHK(hipEventCreate(&c->ev_scan0));
-        HIPCHK(hipEventCreate(&c->ev_scan1));
+        HIPCHK(c->ev_rounds.create(hipEventDisableTiming));
+        HIPCHK(c->ev_comm.create(hipEventDisableTiming));
+        HIPCHK(c->ev_t_rounds.create());
+        HIPCHK(c->ev_t_comm.create());
+        HIPCHK(c->ev_scan0.create());
+        HIPCHK(c->ev_scan1.create());
         HIPCHK(c->scal.resize(yue_host::kNllSlotsHost + 8));
         return YUE_OK;
     };
@@ -47,43 +47,8 @@ int yue_ctx_destroy(yue_ctx *c) {
     if (c->comm_stream) (void)hipStreamSynchronize(c->comm_stream);
     yue_comm_release(c);
     if (c->comm_stream) (void)hipStreamDestroy(c->comm_stream);
-    if (c->ev_rounds) (void)hipEventDestroy(c->ev_rounds);
-    if (c->ev_comm) (void)hipEventDestroy(c->ev_comm);
-    if (c->ev_t_rounds) (void)hipEventDestroy(c->ev_t_rounds);
-    if (c->ev_t_comm) (void)hipEventDestroy(c->ev_t_comm);
-    if (c->ev_scan0) (void)hipEventDestroy(c->ev_scan0);
-    if (c->ev_chain0) (void)hipEventDestroy(c->ev_chain0);
-    if (c->ev_chain1) (void)hipEventDestroy(c->ev_chain1);
-    if (c->ev_scan1) (void)hipEventDestroy(c->ev_scan1);
-    for (auto &pr : c->ev_pool) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
-    c->P.release(); c->Q.release(); c->dP.release(); c->dQ.release(); c->margins.release();
-    c->cnt0.release(); c->cnt1.release(); c->cntp0.release(); c->cntp1.release();
-    c->tab0.release(); c->tab1.release();
-    c->meta_i.release(); c->meta_j.release(); c->round_rows.release(); c->d_bounds.release(); c->fold.release(); c->bk_touch.release(); c->bk_ptr.release();
-    c->ev_u.release(); c->ev_i.release(); c->ev_j.release(); c->indices.release(); c->indptr.release();
-    c->xu.release(); c->xi.release(); c->xj.release(); c->xk.release(); c->x_loss.release(); c->scal.release();
-    c->aU_m.release(); c->aU_v.release(); c->aV_m.release(); c->aV_v.release();
-    c->s_users.release(); c->s_ids.release(); c->s_mask_idx.release(); c->s_flags.release();
-    c->s_mask_ptr.release(); c->s_scores.release(); c->s_row.release(); c->s_norms.release(); c->s_work.release(); c->s_qb.release(); c->s_masks.release(); c->s_few.release(); c->s_few_ids.release(); c->s_few_scores.release();
-    c->fP.release(); c->fBi.release(); c->f_coef.release(); c->f_x.release(); c->f_hist.release(); c->f_scores.release();
-    c->f_out_sc.release(); c->fQ.release(); c->f_ptr.release(); c->f_items.release(); c->f_negs.release(); c->f_ids.release(); c->f_flags.release();
-    c->f_uq_ptr.release(); c->f_neg_ptr.release(); c->f_uq_items.release(); c->f_loc_i.release(); c->f_loc_j.release();
-    c->f_wq.release(); c->f_dQ.release(); c->f_wp.release(); c->f_wb.release(); c->f_dP.release(); c->f_dB.release();
-    c->ch_key.release(); c->ch_val.release(); c->ch_key2.release(); c->ch_val2.release(); c->ch_seg.release(); c->ch_ord_i.release(); c->ch_ord_j.release();
-    c->ch_head.release(); c->ch_incl.release(); c->ch_ord_u.release(); c->ch_rkey.release(); c->ch_rval.release(); c->ch_run_ptr.release(); c->d_ev_ptr.release();
-    c->ch_run_u.release(); c->ch_tmp.release(); c->ch_Qv.release(); c->ch_Pv.release(); c->ch_ctl.release(); c->ch_stats.release();
-    yue_host::wrmf_release(c);
-    yue_host::knn_release(c);
-    yue_host::ipf_release(c);
-    yue_host::expo_release(c);
-    yue_host::cof_release(c);
-    yue_host::cnet_release(c);
-    yue_host::s2v_release(c);
-    yue_host::lgcn_release(c);
-    yue_host::ngcf_release(c);
-    yue_host::cdae_release(c);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;                             // buffers, events and subsystem states go with their members
     return YUE_OK;
 }
 

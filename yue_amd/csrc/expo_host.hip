@@ -14,36 +14,11 @@ struct yue_expo {
     DevBuf<double> ws, part;
     DevBuf<int> status, rows;        // rows: the caller's list of yue_expo_gram_rows
     int64_t n_mu = 0;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> gram_ev;     // brackets of the Gram launches of the last half-sweep
+    Event ev[2];
+    std::vector<std::pair<Event, Event>> gram_ev;     // brackets of the Gram launches of the last half-sweep
 };
 
-namespace yue_host {
-
-void expo_release(yue_ctx *c) {
-    yue_expo *x = c->expo;
-    if (!x) return;
-    x->mu.release(); x->gws.release(); x->ws.release(); x->part.release(); x->status.release(); x->rows.release();
-    for (auto &e : x->ev) if (e) (void)hipEventDestroy(e);
-    for (auto &p : x->gram_ev) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
-    delete x;
-    c->expo = nullptr;
-}
-
-}  // namespace yue_host
-
 namespace {
-
-int expo_state(yue_ctx *c, yue_expo **out) {
-    if (!c->expo) {
-        HIPCHK(hipSetDevice(c->device));
-        yue_expo *x = new yue_expo();
-        c->expo = x;
-        for (auto &e : x->ev) HIPCHK(hipEventCreate(&e));
-    }
-    *out = c->expo;
-    return YUE_OK;
-}
 
 // column splits of a dense kernel: enough workgroups to fill the device for small shapes, a function of the shapes alone
 int splits_for(int64_t groups, int64_t cols, int64_t *cols_per_split) {
@@ -96,7 +71,7 @@ int common_checks(yue_ctx *c, const char *who, yue_expo **x, double lam_y) {
     if (!c || !c->have_factors) return fail(YUE_ERR_ARG, std::string(who) + ": no factors uploaded");
     if (c->k > yue::kWrmfMaxK) return fail(YUE_ERR_ARG, std::string(who) + ": k = " + std::to_string(c->k) + " is not supported (ExpoMF solves need 1 <= k <= 128)");
     if (c->m >= (1 << 26) || c->n >= (1 << 26)) return fail(YUE_ERR_ARG, std::string(who) + ": m and n must be below 2^26");
-    *x = c->expo;
+    *x = c->expo.get();
     if (!*x || (*x)->n_mu != c->n) return fail(YUE_ERR_ARG, std::string(who) + ": call yue_expo_set_mu first (n values)");
     if (!std::isfinite(lam_y) || !(lam_y > 0)) return fail(YUE_ERR_ARG, std::string(who) + ": lam_y must be finite and positive");
     return YUE_OK;
@@ -118,7 +93,7 @@ int yue_expo_set_mu(yue_ctx *c, const float *mu, int64_t n) {
     for (int64_t i = 0; i < n; ++i)
         if (!(mu[i] > 0.0f && mu[i] < 1.0f)) return fail(YUE_ERR_ARG, "yue_expo_set_mu: mu[" + std::to_string(i) + "] is outside (0, 1)");
     yue_expo *x = nullptr;
-    int rc = expo_state(c, &x);
+    int rc = yue_host::state(c, c->expo, &x);
     if (rc) return rc;
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(x->mu.resize((size_t)n));
@@ -166,15 +141,10 @@ int yue_expo_half_sweep(yue_ctx *c, int side, double lam, double lam_y, int mu_p
     HIPCHK(x->status.resize(1));
     a.gws = x->gws.p; a.ws = x->ws.p; a.status = x->status.p;
     const int64_t batches = (v.rows + rows_batch - 1) / rows_batch;
-    while ((int64_t)x->gram_ev.size() < batches) {
-        hipEvent_t e0, e1;
-        HIPCHK(hipEventCreate(&e0));
-        HIPCHK(hipEventCreate(&e1));
-        x->gram_ev.push_back({e0, e1});
-    }
+    if ((int64_t)x->gram_ev.size() < batches) x->gram_ev.resize((size_t)batches);
     const int none = INT_MAX;
     HIPCHK(hipMemcpyAsync(x->status.p, &none, sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipEventRecord(x->ev[0], c->stream));
+    HIPCHK(x->ev[0].record(c->stream));
     if (v.chunks > 0) hipLaunchKernelGGL(yue::k_expo_chunk, dim3((unsigned)v.chunks), dim3(yue::kWrmfThreads), 0, c->stream, a);
     const int lds_gram = yue::expo_dyn_lds(k), lds_solve = yue::wrmf_dyn_lds(k);
     HIPCHK(hipFuncSetAttribute((const void *)yue::k_expo_solve, hipFuncAttributeMaxDynamicSharedMemorySize, lds_solve));
@@ -184,27 +154,25 @@ int yue_expo_half_sweep(yue_ctx *c, int side, double lam, double lam_y, int mu_p
         // rows without pairs become 0 in the solve whatever their Gram: they are the last positions of sched and get no tile
         const int64_t dense = std::min<int64_t>(a.pos1, v.n_nonempty) - a.pos0;
         const dim3 grid((unsigned)((std::max<int64_t>(dense, 0) + yue::kExpoTile - 1) / yue::kExpoTile), (unsigned)gy, (unsigned)a.splits);
-        HIPCHK(hipEventRecord(x->gram_ev[(size_t)b].first, c->stream));
+        HIPCHK(x->gram_ev[(size_t)b].first.record(c->stream));
         if (grid.x > 0) {
             if ((rc = launch_gram_nb(nb, a, grid, lds_gram, c->stream))) return rc;
         }
-        HIPCHK(hipEventRecord(x->gram_ev[(size_t)b].second, c->stream));
+        HIPCHK(x->gram_ev[(size_t)b].second.record(c->stream));
         hipLaunchKernelGGL(yue::k_expo_solve, dim3((unsigned)(a.pos1 - a.pos0)), dim3(yue::kWrmfThreads), lds_solve, c->stream, a);
     }
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(x->ev[1], c->stream));
+    HIPCHK(x->ev[1].record(c->stream));
     int status = INT_MAX;
     HIPCHK(hipMemcpyAsync(&status, x->status.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    float ms = 0.0f;
-    HIPCHK(hipEventElapsedTime(&ms, x->ev[0], x->ev[1]));
-    c->expo_ns[0] = (int64_t)(1e6 * (double)ms);
-    double gram_ms = 0.0;
+    HIPCHK(yue_host::elapsed(x->ev[0], x->ev[1], &c->expo_ns[0]));
+    double gram_ms = 0.0, ms = 0.0;
     for (int64_t b = 0; b < batches; ++b) {
-        HIPCHK(hipEventElapsedTime(&ms, x->gram_ev[(size_t)b].first, x->gram_ev[(size_t)b].second));
-        gram_ms += (double)ms;
+        HIPCHK(yue_host::elapsed(x->gram_ev[(size_t)b].first, x->gram_ev[(size_t)b].second, &ms));
+        gram_ms += ms;
     }
-    c->expo_ns[1] = (int64_t)(1e6 * gram_ms);
+    c->expo_ns[1] = yue_host::ns_of(gram_ms);
     c->expo_batches = batches;
     if (status != INT_MAX)
         return fail(YUE_ERR_ARG, std::string("yue_expo_half_sweep: non-positive pivot in the Cholesky factorisation of ") + (side == 0 ? "user" : "item") +
@@ -273,15 +241,13 @@ int yue_expo_update_mu(yue_ctx *c, double pa, double pb, double lam_y) {
     HIPCHK(x->part.resize((size_t)a.splits * (size_t)c->n));
     const int lds = (yue::kExpoChunk + yue::kExpoTile) * yue::expo_ld(k) * 4;
     HIPCHK(hipFuncSetAttribute((const void *)yue::k_expo_asum, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    HIPCHK(hipEventRecord(x->ev[0], c->stream));
+    HIPCHK(x->ev[0].record(c->stream));
     hipLaunchKernelGGL(yue::k_expo_asum, dim3((unsigned)tiles, (unsigned)a.splits), dim3(256), lds, c->stream, a, x->part.p);
     hipLaunchKernelGGL(yue::k_expo_mu, dim3((unsigned)((c->n + 3) / 4)), dim3(256), 0, c->stream, a, (const double *)x->part.p, a.splits, pa, pb, x->mu.p);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(x->ev[1], c->stream));
+    HIPCHK(x->ev[1].record(c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    float ms = 0.0f;
-    HIPCHK(hipEventElapsedTime(&ms, x->ev[0], x->ev[1]));
-    c->expo_ns[0] = (int64_t)(1e6 * (double)ms);
+    HIPCHK(yue_host::elapsed(x->ev[0], x->ev[1], &c->expo_ns[0]));
     c->expo_ns[1] = 0;
     return YUE_OK;
 }

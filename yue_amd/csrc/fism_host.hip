@@ -168,10 +168,10 @@ int yue_fism_rounds(yue_ctx *c, const int64_t *user_ptr, int64_t m, const int32_
                 hipLaunchKernelGGL(yue::k_fism_count_round, dim3((unsigned)std::min(m, round_users)), dim3(64), 0, c->stream, a, la.neg_ptr, (int64_t)0, std::min(m, round_users), cnt[0]);
             }
 #ifdef YUE_FISM_STAMPS
-            unsigned long long *d_stamps = nullptr;
-            HIPCHK(hipMalloc(&d_stamps, 8 * sizeof(unsigned long long)));
-            HIPCHK(hipMemsetAsync(d_stamps, 0, 8 * sizeof(unsigned long long), c->stream));
-            la.stamps = d_stamps;
+            DevBuf<unsigned long long> d_stamps;                 // freed on every return below
+            HIPCHK(d_stamps.resize(8));
+            HIPCHK(hipMemsetAsync(d_stamps.p, 0, 8 * sizeof(unsigned long long), c->stream));
+            la.stamps = d_stamps.p;
 #endif
             // the round-start rows beside the working rows when both fit in the CU's LDS (a wave has the CU to itself anyway)
             // -- as long as that leaves the round's waves resident at once: a round larger than the CUs can hold with the doubled
@@ -206,8 +206,7 @@ int yue_fism_rounds(yue_ctx *c, const int64_t *user_ptr, int64_t m, const int32_
 #ifdef YUE_FISM_STAMPS
             {
                 unsigned long long st[8];
-                HIPCHK(hipMemcpy(st, d_stamps, sizeof st, hipMemcpyDeviceToHost));
-                HIPCHK(hipFree(d_stamps));
+                HIPCHK(hipMemcpy(st, d_stamps.p, sizeof st, hipMemcpyDeviceToHost));
                 const char *names[6] = {"count + find rows", "copy-in", "history sum", "draws", "item-history rows", "rows back / differences"};
                 for (int q = 0; q < 6; ++q) std::fprintf(stderr, "fism stamps: %-24s %8.2f us per wave\n", names[q], st[7] ? 0.01 * (double)st[q] / (double)st[7] : 0.0);
             }

@@ -12,14 +12,8 @@
 namespace gcn {
 
 using yue_host::fail;
+using yue_host::upload;
 using yue_host::with_kr;
-
-template <typename T>
-int upload(DevBuf<T> &buf, const T *src, int64_t count) {
-    HIPCHK(buf.resize((size_t)std::max<int64_t>(count, 1)));
-    if (count > 0) HIPCHK(hipMemcpy(buf.p, src, (size_t)count * sizeof(T), hipMemcpyHostToDevice));
-    return YUE_OK;
-}
 
 // one sparse matrix: CSR on host (row pointers) and device, and the hub rows' parts for the threshold they were built with.
 // The hub parts' partial rows are the caller's buffer: a model with two matrices shares one, sized for the larger.
@@ -31,9 +25,6 @@ struct Graph {
     int rpw = 1;                                     // rows per wave of k_lgcn_rows
     int64_t hub_built = -1, H = 0, parts = 0;        // hub rows, rebuilt when the model's hub option differs from hub_built
     DevBuf<int64_t> hub_row, hub_part_ptr, part_beg, part_end;
-    void release() {
-        ptr.release(); col.release(); w.release(); hub_row.release(); hub_part_ptr.release(); part_beg.release(); part_end.release();
-    }
 };
 
 // `who` names the model and its option in the refusal ("yue_lgcn: lgcn_hub")
@@ -108,7 +99,6 @@ struct Batch {
     std::vector<int64_t> h_seg_ptr, h_seg_row;
     std::vector<int32_t> h_ent;
     std::vector<double> h_loss;
-    void release() { coef.release(); loss.release(); seg_ptr.release(); seg_row.release(); ent.release(); }
 };
 
 // the triplets to the device, then the 3 T (row of F, triplet, role) entries by row, a row's entries in triplet order: the
@@ -167,20 +157,15 @@ inline int batch_loss(yue_ctx *c, Batch &b, int64_t T, double *loss_out) {
 // time stamps of one call: event t closes an interval that belongs to phase[t] (the first stamp opens the first interval).
 // Events are created on demand and kept; a call starts over with stamps = 0.
 struct PhaseTimer {
-    std::vector<hipEvent_t> ev;
+    std::vector<Event> ev;
     std::vector<int> phase;
     size_t stamps = 0;
-    void release() { for (auto &e : ev) if (e) (void)hipEventDestroy(e); ev.clear(); phase.clear(); stamps = 0; }
 };
 
 inline int stamp(yue_ctx *c, PhaseTimer &t, int phase) {
-    if (t.stamps == t.ev.size()) {
-        hipEvent_t e = nullptr;
-        HIPCHK(hipEventCreate(&e));
-        t.ev.push_back(e); t.phase.push_back(0);
-    }
+    if (t.stamps == t.ev.size()) { t.ev.emplace_back(); t.phase.push_back(0); }
     t.phase[t.stamps] = phase;
-    HIPCHK(hipEventRecord(t.ev[t.stamps++], c->stream));
+    HIPCHK(t.ev[t.stamps++].record(c->stream));
     return YUE_OK;
 }
 
@@ -188,9 +173,9 @@ inline int stamp(yue_ctx *c, PhaseTimer &t, int phase) {
 inline int read_times(const PhaseTimer &t, int64_t *ns, int phases) {
     for (int p = 0; p < phases; ++p) ns[p] = 0;
     for (size_t s = 1; s < t.stamps; ++s) {
-        float ms = 0.0f;
-        HIPCHK(hipEventElapsedTime(&ms, t.ev[s - 1], t.ev[s]));
-        ns[t.phase[s]] += (int64_t)(1e6 * (double)ms);
+        int64_t interval = 0;
+        HIPCHK(yue_host::elapsed(t.ev[s - 1], t.ev[s], &interval));
+        ns[t.phase[s]] += interval;
     }
     return YUE_OK;
 }

@@ -14,6 +14,10 @@
 //   cdae_host.hip   CDAE (sparse encoder, sampled decoder, gradients regrouped by item, dense Adam on five variables)
 //   gcn_host.hpp    what those two share (header only): the graph on the device and its hub parts, a product's launches, the
 //                   minibatch, the phase timer
+// Ownership: every device allocation is a DevBuf, every event an Event, every subsystem's state a StatePtr
+// member of the context made by state(); each frees itself with its owner, so yue_ctx_destroy ends in `delete c` and no unit
+// keeps a list of things to release.  The raw HIP calls for both stand in this header and nowhere else, as do upload / download
+// (blocking copies into and out of a DevBuf) and elapsed (the time between two events) -- tests/test_host_ownership.py.
 #pragma once
 #include "../../include/yue_hip.h"
 
@@ -24,8 +28,10 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 struct ncclComm;
@@ -51,10 +57,20 @@ int fail(int code, const std::string &msg);          // sets the thread-local me
             return yue_host::fail(YUE_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
+// One device allocation, freed with its owner (move-only; an empty one makes no HIP call, also not when it is destroyed).
 template <typename T>
 struct DevBuf {
     T *p = nullptr;
     size_t n = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept {
+        if (this != &o) { release(); p = o.p; n = o.n; o.p = nullptr; o.n = 0; }
+        return *this;
+    }
+    ~DevBuf() { release(); }
     hipError_t resize(size_t count) {
         if (count <= n && p) return hipSuccess;
         if (p) { hipError_t e = hipFree(p); p = nullptr; n = 0; if (e != hipSuccess) return e; }
@@ -66,6 +82,56 @@ struct DevBuf {
     void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
 };
 
+// blocking copies of `count` elements: up into a buffer that holds max(count, 1), so that its pointer is never null
+// afterwards; down only where the caller wants them (dst may be null)
+template <typename T>
+int upload(DevBuf<T> &buf, const T *src, int64_t count) {
+    HIPCHK(buf.resize((size_t)std::max<int64_t>(count, 1)));
+    if (count > 0) HIPCHK(hipMemcpy(buf.p, src, (size_t)count * sizeof(T), hipMemcpyHostToDevice));
+    return YUE_OK;
+}
+template <typename T>
+int upload(DevBuf<T> &buf, const std::vector<T> &src) { return upload(buf, src.data(), (int64_t)src.size()); }
+template <typename T>
+int download(T *dst, const DevBuf<T> &src, size_t count) {
+    if (dst && count > 0) HIPCHK(hipMemcpy(dst, src.p, count * sizeof(T), hipMemcpyDeviceToHost));
+    return YUE_OK;
+}
+
+// One event, destroyed with its owner (move-only, so that a std::vector of them works).  record() creates it the first time;
+// an event something may wait for before its first record (the context's ev_rounds / ev_comm) is created by name.
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(const Event &) = delete;
+    Event &operator=(const Event &) = delete;
+    Event(Event &&o) noexcept : e(o.e) { o.e = nullptr; }
+    Event &operator=(Event &&o) noexcept { std::swap(e, o.e); return *this; }
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    hipError_t create(unsigned flags = hipEventDefault) { return e ? hipSuccess : hipEventCreateWithFlags(&e, flags); }
+    hipError_t record(hipStream_t s) {
+        const hipError_t rc = create();
+        return rc != hipSuccess ? rc : hipEventRecord(e, s);
+    }
+    operator hipEvent_t() const { return e; }
+};
+
+// The time between two recorded events whose stream has been waited for: in milliseconds as a double (for sums of several
+// intervals, converted once), or in nanoseconds as every *_ns field holds one interval.
+inline hipError_t elapsed(hipEvent_t from, hipEvent_t to, double *ms) {
+    float f = 0.0f;
+    const hipError_t rc = hipEventElapsedTime(&f, from, to);
+    if (rc == hipSuccess) *ms = (double)f;
+    return rc;
+}
+inline int64_t ns_of(double ms) { return (int64_t)(1e6 * ms); }
+inline hipError_t elapsed(hipEvent_t from, hipEvent_t to, int64_t *ns) {
+    double ms = 0.0;
+    const hipError_t rc = elapsed(from, to, &ms);
+    if (rc == hipSuccess) *ns = ns_of(ms);
+    return rc;
+}
+
 constexpr int kNllSlotsHost = 1024;   // == yue::kNllSlots (bpr_device.hpp; checked where both are visible)
 constexpr int kHeaderSlackHost = 16;  // == yue::kHeaderSlack (round_kernels.hpp)
 constexpr int kMetaStageMaxHost = 64; // == yue::kMetaStageMax (round_kernels.hpp)
@@ -73,6 +139,11 @@ constexpr int kMetaStageMaxHost = 64; // == yue::kMetaStageMax (round_kernels.hp
 constexpr int kWrmfStageHost = 32;    // == yue::kWrmfStage (wrmf_kernels.hpp)
 constexpr int kKnnRangeHost = 4096, kKnnMaxKHost = 256, kKnnGatherHost = 2048;   // == yue::kKnnRange, kKnnMaxK, kKnnGather (knn_kernels.hpp)
 constexpr int kCofRangeHost = 8192;   // == yue::kCofRange (cof_kernels.hpp)
+
+// A subsystem's state as the context holds it: yue_host::state() in the subsystem's own unit creates it and supplies the
+// deleter, so that whoever sees only the declaration (options_host.hip) can still destroy a context.
+template <class T>
+using StatePtr = std::unique_ptr<T, void (*)(T *)>;
 
 inline int kr_of(int k) { return k <= 64 ? 1 : k <= 128 ? 2 : 4; }   // registers per lane per row (64 lanes)
 
@@ -89,6 +160,7 @@ auto with_kr(int k, F &&f) {
 }  // namespace yue_host
 
 using yue_host::DevBuf;
+using yue_host::Event;
 
 struct yue_ctx {
     int device = 0;
@@ -166,7 +238,7 @@ struct yue_ctx {
     int opt_round_meta = 1;              // 0: the epoch path counts touches inside the round launches (k_round) as the explicit-rounds path does
     // kernel timing
     int timing_stride = 0;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
+    std::vector<std::pair<Event, Event>> ev_pool;
     std::vector<int64_t> ev_triplets, ev_launches;
     size_t ev_used = 0;
     // FISM (parity path): item-history factors (f64), item factors (f32), item bias (f64)
@@ -203,13 +275,13 @@ struct yue_ctx {
     int opt_chain_waves = 0;             // workgroups per CU of the persistent launch (0: what fits, at most 8)
     int64_t opt_chain_spin = 0;          // polls per wait before a wave gives up (0: 2^22)
     int64_t chain_runs = 0, chain_waves = 0, chain_groups = 0, chain_kernel_us = 0, replay_levels = 0;
-    hipEvent_t ev_chain0 = nullptr, ev_chain1 = nullptr;   // brackets of the dataflow launch (read-only option chain_last_us)
+    Event ev_chain0, ev_chain1;   // brackets of the dataflow launch (read-only option chain_last_us)
     // RCCL
     ncclComm *comm = nullptr;              // ncclComm_t (comm.hip)
     int rank = 0, nranks = 1;
     hipStream_t comm_stream = nullptr;   // (all-reduce +) user-row apply of yue_bpr_epoch run here, beside the next rounds
-    hipEvent_t ev_rounds = nullptr, ev_comm = nullptr;
-    hipEvent_t ev_t_rounds = nullptr, ev_t_comm = nullptr;   // timing pair of the last epoch on a communicator: end of its round launches / end of its last apply
+    Event ev_rounds, ev_comm;
+    Event ev_t_rounds, ev_t_comm;   // timing pair of the last epoch on a communicator: end of its round launches / end of its last apply
     // TEST SEAM (libyue_hip_seam.so only, make test-seam: the product library has no way to set these): the collective of
     // reduce_user_block / yue_allreduce_f64 as a host-staged sum through a callback, so that the 2-rank block / group /
     // stream logic of yue_bpr_epoch runs on a one-GPU box (tests/test_gpu_multi.py).  dtype 0 = float, 1 = double.
@@ -220,39 +292,39 @@ struct yue_ctx {
     int64_t comm_collectives = 0;
     double comm_bytes = 0.0, comm_wait_ms = 0.0;
     int comm_version = 0, comm_nranks_reported = 0;
-    hipEvent_t ev_scan0 = nullptr, ev_scan1 = nullptr;      // brackets of the scoring kernel (yue_get_scan_stats)
-    yue_wrmf *wrmf = nullptr;            // WRMF state (yue_wrmf_set_pairs), owned by wrmf_host.hip
+    Event ev_scan0, ev_scan1;      // brackets of the scoring kernel (yue_get_scan_stats)
+    yue_host::StatePtr<yue_wrmf> wrmf{nullptr, nullptr};   // WRMF state (yue_wrmf_set_pairs), owned by wrmf_host.hip
     int64_t opt_wrmf_long_pairs = 2048;  // WRMF: rows with more pairs are summed by several workgroups (chunks of this many pairs) before their solve; read by yue_wrmf_set_pairs and by CoFactor's schedule
     int64_t wrmf_ns[2] = {0, 0};         // device time of the last half-sweep, of its long-row chunks (read-only options wrmf_last_ns / wrmf_last_long_ns)
-    yue_knn *knn = nullptr;              // UserKNN state (yue_knn_set_pairs), owned by knn_host.hip
+    yue_host::StatePtr<yue_knn> knn{nullptr, nullptr};   // UserKNN state (yue_knn_set_pairs), owned by knn_host.hip
     int opt_knn_range = yue_host::kKnnRangeHost, opt_knn_gather = yue_host::kKnnGatherHost;   // UserKNN: candidate users per counting pass, entries per scoring chunk (tests lower them to reach the multi-pass paths)
     int64_t knn_ns = 0, knn_chunked_users = 0;   // device time of the last neighbours / topn / predict call; users of the last topn scored in item-range chunks (read-only options knn_last_*)
-    yue_ipf *ipf = nullptr;              // IPF state (yue_ipf_set_graph), owned by ipf_host.hip
+    yue_host::StatePtr<yue_ipf> ipf{nullptr, nullptr};   // IPF state (yue_ipf_set_graph), owned by ipf_host.hip
     int opt_ipf_slots = 1024;            // IPF: workgroups (queries in flight) of one yue_ipf_topn launch
     int64_t ipf_ns = 0;                  // device time of the last topn / predict launch (read-only option ipf_last_ns)
-    yue_expo *expo = nullptr;            // ExpoMF state (yue_expo_set_mu), owned by expo_host.hip
+    yue_host::StatePtr<yue_expo> expo{nullptr, nullptr};   // ExpoMF state (yue_expo_set_mu), owned by expo_host.hip
     int64_t opt_expo_gram_mb = 512;      // ExpoMF: budget of the per-row Gram workspace, MiB: a half-sweep runs in batches of rows that fit
     int64_t expo_ns[2] = {0, 0};         // device time of the last half-sweep / mu update, of its dense MFMA kernel(s) (read-only options expo_last_ns / expo_last_gram_ns)
     int64_t expo_batches = 0;            // row batches of the last half-sweep (read-only option expo_last_batches)
-    yue_cof *cof = nullptr;              // CoFactor state (yue_cof_*), owned by cof_host.hip
+    yue_host::StatePtr<yue_cof> cof{nullptr, nullptr};   // CoFactor state (yue_cof_*), owned by cof_host.hip
     int64_t opt_cof_cooccur_mb = 1024;   // CoFactor: bound of the co-occurrence CSR (idx + cnt: 8 bytes per entry), MiB
     int64_t opt_cof_pass_items = yue_host::kCofRangeHost;   // ... items counted per pass
     int opt_cof_level_timing = 0;        // ... 1: time every level's launch (tools/cofactor_bench.py)
     int64_t cof_ns[2] = {0, 0};          // device time of the last co-occurrence build / item sweep, of the sweep's levels of fewer than 256 rows (0 unless timed) (read-only options cof_last_ns / cof_last_small_ns)
-    yue_cnet *cnet = nullptr;            // CUNE user-network state (yue_cnet_*), owned by cnet_host.hip
+    yue_host::StatePtr<yue_cnet> cnet{nullptr, nullptr};   // CUNE user-network state (yue_cnet_*), owned by cnet_host.hip
     int64_t cnet_ns = 0;                 // device time of the last walks / embed / friends call (read-only option cnet_last_ns)
-    yue_s2v *s2v = nullptr;              // Song2vec state (yue_s2v_*), owned by s2v_host.hip
+    yue_host::StatePtr<yue_s2v> s2v{nullptr, nullptr};   // Song2vec state (yue_s2v_*), owned by s2v_host.hip
     int opt_s2v_schedule = 1;            // Song2vec: 0 = one wave walks all steps, 1 = one launch per dependency level
     int64_t s2v_ns = 0;                  // device time of the last yue_s2v_epoch (read-only option s2v_last_ns)
-    yue_lgcn *lgcn = nullptr;            // LightGCN state (yue_lgcn_*), owned by lgcn_host.hip
+    yue_host::StatePtr<yue_lgcn> lgcn{nullptr, nullptr};   // LightGCN state (yue_lgcn_*), owned by lgcn_host.hip
     int64_t opt_lgcn_hub = 1024;         // LightGCN: rows with more neighbours are cut into parts of this many, one wave each (lgcn_kernels.hpp)
     int64_t lgcn_hubs = 0, lgcn_parts = 0;   // ... such rows and their parts in the last call (read-only options lgcn_last_hubs / lgcn_last_parts)
     int64_t lgcn_ns[4] = {0, 0, 0, 0};   // device time of the last call's forward, minibatch, backward and Adam phases (read-only options lgcn_last_*_ns)
-    yue_ngcf *ngcf = nullptr;            // NGCF state (yue_ngcf_*), owned by ngcf_host.hip
+    yue_host::StatePtr<yue_ngcf> ngcf{nullptr, nullptr};   // NGCF state (yue_ngcf_*), owned by ngcf_host.hip
     int64_t opt_ngcf_hub = 1024;         // NGCF: as lgcn_hub, for the graph and its transpose
     int64_t ngcf_hubs = 0, ngcf_parts = 0;   // ... hub rows and parts of both matrices in the last call (read-only options ngcf_last_hubs / ngcf_last_parts)
     int64_t ngcf_ns[6] = {0, 0, 0, 0, 0, 0};   // device time of the last call's gather, dense, batch, backward, wgrad and adam phases (read-only options ngcf_last_*_ns)
-    yue_cdae *cdae = nullptr;            // CDAE state (yue_cdae_*), owned by cdae_host.hip
+    yue_host::StatePtr<yue_cdae> cdae{nullptr, nullptr};   // CDAE state (yue_cdae_*), owned by cdae_host.hip
     int64_t opt_cdae_hub = 1024;         // CDAE: encoder rows and regrouped segments with more entries are cut into parts of this many (the default is lgcn_hub's, unmeasured here)
     int64_t cdae_hubs = 0, cdae_parts = 0;   // ... such rows / segments and their parts in the last call (read-only options cdae_last_hubs / cdae_last_parts)
     int64_t cdae_saturated = 0;          // sampled outputs with y_pred == 1.0f in the last call (read-only option cdae_last_saturated)
@@ -276,9 +348,19 @@ int reduce_user_block(yue_ctx *c, int64_t first, int64_t count, hipStream_t stre
 // chain_host.hip: exact sequential semantics over the uploaded events (negatives in ev_j) / over the stream in xu, xi, xj
 int chain_epoch(yue_ctx *c, double lr, double regU, double regI);
 int chain_stream(yue_ctx *c, int64_t T, double lr, double regU, double regI);
+// The subsystem's state for an entry point of its own unit (the only place that sees the type whole): made on the context's
+// device when there is none yet, and destroyed with the context.
+template <class T>
+int state(yue_ctx *c, StatePtr<T> &slot, T **out) {
+    if (!slot) {
+        HIPCHK(hipSetDevice(c->device));
+        slot = StatePtr<T>(new T(), [](T *s) { delete s; });
+    }
+    *out = slot.get();
+    return YUE_OK;
+}
 // The subsystems below: what yue_get_option reads from one of them without a state is 0.
-// wrmf_host.hip: frees the WRMF state; a side's long rows (read-only options wrmf_long_rows_user / _item)
-void wrmf_release(yue_ctx *c);
+// wrmf_host.hip: a side's long rows (read-only options wrmf_long_rows_user / _item)
 int64_t wrmf_long_rows(const yue_ctx *c, int side);
 // ... the uploaded pairs of one side (0: user rows, 1: item rows) for the other ALS solver (expo_host.hip); false when
 // yue_wrmf_set_pairs has not run for the context's current factors
@@ -292,24 +374,9 @@ bool wrmf_pairs_view(const yue_ctx *c, int side, WrmfPairsView *v);
 // ... and the fp32-rounded F^T F of the side's fixed factors (0: Y^T Y, 1: X^T X), queued on the context's stream into the
 // WRMF state's slot-major buffer (cof_host.hip)
 int wrmf_gram(yue_ctx *c, int side, const double **G);
-// knn_host.hip, ipf_host.hip, expo_host.hip, cnet_host.hip: free the subsystem's state
-void knn_release(yue_ctx *c);
-void ipf_release(yue_ctx *c);
-void expo_release(yue_ctx *c);
-void cnet_release(yue_ctx *c);
-// cof_host.hip: frees the CoFactor state; levels of the uploaded SPPMI, entries of the co-occurrence CSR (read-only options
-// cof_levels / cof_cooccur_nnz)
-void cof_release(yue_ctx *c);
+// cof_host.hip: levels of the uploaded SPPMI, entries of the co-occurrence CSR (read-only options cof_levels / cof_cooccur_nnz)
 int64_t cof_levels(const yue_ctx *c);
 int64_t cof_cooccur_nnz(const yue_ctx *c);
-// s2v_host.hip: frees the Song2vec state; dependency levels of the steps (which = 0) / the pairs (1) (read-only options
-// s2v_levels_steps / s2v_levels_pairs)
-void s2v_release(yue_ctx *c);
+// s2v_host.hip: dependency levels of the steps (which = 0) / the pairs (1) (read-only options s2v_levels_steps / s2v_levels_pairs)
 int64_t s2v_levels(const yue_ctx *c, int which);
-// lgcn_host.hip: frees the LightGCN state (its options are rows of the option table)
-void lgcn_release(yue_ctx *c);
-// ngcf_host.hip: frees the NGCF state (its options are rows of the option table)
-void ngcf_release(yue_ctx *c);
-// cdae_host.hip: frees the CDAE state (its options are rows of the option table)
-void cdae_release(yue_ctx *c);
 }  // namespace yue_host

@@ -5,6 +5,7 @@
 #include "ipf_kernels.hpp"
 
 using yue_host::fail;
+using yue_host::upload;
 
 struct yue_ipf {
     int64_t m = 0, n = 0;
@@ -18,37 +19,10 @@ struct yue_ipf {
     DevBuf<unsigned long long> key2, e2, key3, ins, ins_out;
     DevBuf<double> r2u, r2s, score, scores_out;
     DevBuf<int32_t> touch2, touch3, users, ids_out, len_out;
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    Event ev[2];
 };
 
-namespace yue_host {
-
-void ipf_release(yue_ctx *c) {
-    yue_ipf *g = c->ipf;
-    if (!g) return;
-    for (auto *b : {&g->u_ptr, &g->s_ptr, &g->hu_ptr, &g->hs_ptr}) b->release();
-    for (auto *b : {&g->u_items, &g->s_items, &g->hu_users, &g->hs_users, &g->hs_pos, &g->touch2, &g->touch3, &g->users, &g->ids_out, &g->len_out}) b->release();
-    for (auto *b : {&g->w_user, &g->w_sess, &g->p_i2u, &g->p_i2s, &g->r2u, &g->r2s, &g->score, &g->scores_out}) b->release();
-    for (auto *b : {&g->key2, &g->e2, &g->key3, &g->ins, &g->ins_out}) b->release();
-    for (auto &e : g->ev) if (e) (void)hipEventDestroy(e);
-    delete g;
-    c->ipf = nullptr;
-}
-
-}  // namespace yue_host
-
 namespace {
-
-int ipf_state(yue_ctx *c, yue_ipf **out) {
-    if (!c->ipf) {
-        HIPCHK(hipSetDevice(c->device));
-        yue_ipf *g = new yue_ipf();
-        c->ipf = g;
-        for (auto &e : g->ev) HIPCHK(hipEventCreate(&e));
-    }
-    *out = c->ipf;
-    return YUE_OK;
-}
 
 // ptr[rows+1] from 0, non-decreasing; ids in [0, bound); rows no longer than max_row; distinct within a row when asked
 int check_lists(const int64_t *ptr, const int32_t *ids, int64_t rows, int64_t bound, int64_t max_row, bool distinct,
@@ -69,13 +43,6 @@ int check_lists(const int64_t *ptr, const int32_t *ids, int64_t rows, int64_t bo
                 mark[(size_t)ids[e]] = r;
             }
         }
-    return YUE_OK;
-}
-
-template <typename T>
-int upload(DevBuf<T> &buf, const T *src, int64_t count) {
-    HIPCHK(buf.resize((size_t)std::max<int64_t>(count, 1)));
-    if (count > 0) HIPCHK(hipMemcpy(buf.p, src, (size_t)count * sizeof(T), hipMemcpyHostToDevice));
     return YUE_OK;
 }
 
@@ -116,18 +83,16 @@ int launch(yue_ctx *c, yue_ipf *g, int64_t nu, int N, int64_t slots) {
     a.users = g->users.p; a.nu = nu; a.N = N;
     a.ids_out = g->ids_out.p; a.scores_out = g->scores_out.p; a.ins_out = g->ins_out.p; a.len_out = g->len_out.p;
     g->clean = false;
-    HIPCHK(hipEventRecord(g->ev[0], c->stream));
+    HIPCHK(g->ev[0].record(c->stream));
     hipLaunchKernelGGL(yue::k_ipf_rank, dim3((unsigned)slots), dim3(yue::kIpfThreads), 0, c->stream, a);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(g->ev[1], c->stream));
+    HIPCHK(g->ev[1].record(c->stream));
     return YUE_OK;
 }
 
 int finish(yue_ctx *c, yue_ipf *g) {
     HIPCHK(hipStreamSynchronize(c->stream));
-    float ms = 0.0f;
-    HIPCHK(hipEventElapsedTime(&ms, g->ev[0], g->ev[1]));
-    c->ipf_ns = (int64_t)(1e6 * (double)ms);
+    HIPCHK(yue_host::elapsed(g->ev[0], g->ev[1], &c->ipf_ns));
     g->clean = true;
     return YUE_OK;
 }
@@ -135,7 +100,7 @@ int finish(yue_ctx *c, yue_ipf *g) {
 int ready(yue_ctx *c, const char *who, yue_ipf **out) {
     if (!c) return fail(YUE_ERR_ARG, std::string(who) + ": null context");
     if (!c->ipf || c->ipf->m == 0) return fail(YUE_ERR_ARG, std::string(who) + ": call yue_ipf_set_graph first");
-    *out = c->ipf;
+    *out = c->ipf.get();
     return YUE_OK;
 }
 
@@ -163,7 +128,7 @@ int yue_ipf_set_graph(yue_ctx *c, int64_t m, int64_t n, const int64_t *u_ptr, co
         if (hs_pos[e] < 0 || hs_pos[e] > max_holders) return fail(YUE_ERR_ARG, "yue_ipf_set_graph: item2session position out of range (limit 2^26 - 1)");
     HIPCHK(hipSetDevice(c->device));
     yue_ipf *g = nullptr;
-    if ((rc = ipf_state(c, &g))) return rc;
+    if ((rc = yue_host::state(c, c->ipf, &g))) return rc;
     const bool same_shape = g->m == m && g->n == n;
     g->m = 0;                                                    // invalid until everything is up
     if ((rc = upload(g->u_ptr, u_ptr, m + 1)) || (rc = upload(g->u_items, u_items, u_ptr[m])) || (rc = upload(g->s_ptr, s_ptr, m + 1)) ||

@@ -7,6 +7,7 @@
 #include <numeric>
 
 using yue_host::fail;
+using yue_host::upload;
 
 static_assert(yue_host::kKnnRangeHost == yue::kKnnRange && yue_host::kKnnMaxKHost == yue::kKnnMaxK && yue_host::kKnnGatherHost == yue::kKnnGather,
               "the option table's ends of knn_range and knn_gather are the kernels' widths");
@@ -20,36 +21,10 @@ struct yue_knn {
     DevBuf<int32_t> users, ids, len;
     DevBuf<double> scores;
     DevBuf<int> chunked;
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    Event ev[2];
 };
 
-namespace yue_host {
-
-void knn_release(yue_ctx *c) {
-    yue_knn *k = c->knn;
-    if (!k) return;
-    k->u_ptr.release(); k->i_ptr.release(); k->cursor.release(); k->u_items.release(); k->u_counts.release(); k->i_users.release();
-    k->nbr.release(); k->inter.release(); k->uni.release(); k->users.release(); k->ids.release(); k->len.release();
-    k->scores.release(); k->chunked.release();
-    for (auto &e : k->ev) if (e) (void)hipEventDestroy(e);
-    delete k;
-    c->knn = nullptr;
-}
-
-}  // namespace yue_host
-
 namespace {
-
-int knn_state(yue_ctx *c, yue_knn **out) {
-    if (!c->knn) {
-        HIPCHK(hipSetDevice(c->device));
-        yue_knn *k = new yue_knn();
-        c->knn = k;
-        for (auto &e : k->ev) HIPCHK(hipEventCreate(&e));
-    }
-    *out = c->knn;
-    return YUE_OK;
-}
 
 // one direction's CSR: ptr[rows+1] from 0 to nnz, ids sorted-unique in [0, ids_bound), counts (when given) >= 1
 int check_csr(const int64_t *ptr, const int32_t *ids, const int32_t *cnt, int64_t rows, int64_t ids_bound, int64_t nnz, const char *what) {
@@ -67,13 +42,6 @@ int check_csr(const int64_t *ptr, const int32_t *ids, const int32_t *cnt, int64_
     return YUE_OK;
 }
 
-template <typename T>
-int upload(DevBuf<T> &buf, const T *src, int64_t count) {
-    HIPCHK(buf.resize((size_t)std::max<int64_t>(count, 1)));
-    if (count > 0) HIPCHK(hipMemcpy(buf.p, src, (size_t)count * sizeof(T), hipMemcpyHostToDevice));
-    return YUE_OK;
-}
-
 yue::KnnArgs base_args(const yue_ctx *c, const yue_knn *k) {
     yue::KnnArgs a{};
     a.m = k->m; a.n = k->n;
@@ -88,7 +56,7 @@ int ready(yue_ctx *c, const char *who, yue_knn **out) {
     if (!c) return fail(YUE_ERR_ARG, std::string(who) + ": null context");
     if (!c->knn || c->knn->m == 0) return fail(YUE_ERR_ARG, std::string(who) + ": call yue_knn_set_pairs first");
     if (c->knn->K == 0) return fail(YUE_ERR_ARG, std::string(who) + ": call yue_knn_neighbors first");
-    *out = c->knn;
+    *out = c->knn.get();
     return YUE_OK;
 }
 
@@ -118,7 +86,7 @@ int yue_knn_set_pairs(yue_ctx *c, int64_t m, int64_t n, const int64_t *u_ptr, co
     }
     HIPCHK(hipSetDevice(c->device));
     yue_knn *k = nullptr;
-    if ((rc = knn_state(c, &k))) return rc;
+    if ((rc = yue_host::state(c, c->knn, &k))) return rc;
     k->m = 0; k->K = 0;                                          // invalid until everything is up
     if ((rc = upload(k->u_ptr, u_ptr, m + 1)) || (rc = upload(k->u_items, u_items, nnz)) || (rc = upload(k->u_counts, u_counts, nnz)) ||
         (rc = upload(k->i_ptr, i_ptr, n + 1)) || (rc = upload(k->i_users, i_users, nnz)))
@@ -131,7 +99,7 @@ int yue_knn_set_pairs(yue_ctx *c, int64_t m, int64_t n, const int64_t *u_ptr, co
 
 int yue_knn_neighbors(yue_ctx *c, int K, int32_t *nbr_out, int32_t *inter_out, int32_t *union_out) {
     if (!c) return fail(YUE_ERR_ARG, "yue_knn_neighbors: null context");
-    yue_knn *k = c->knn;
+    yue_knn *k = c->knn.get();
     if (!k || k->m == 0) return fail(YUE_ERR_ARG, "yue_knn_neighbors: call yue_knn_set_pairs first");
     if (K < 1 || K > yue::kKnnMaxK) return fail(YUE_ERR_ARG, "yue_knn_neighbors: K = " + std::to_string(K) + " is not supported (1 <= K <= 256)");
     HIPCHK(hipSetDevice(c->device));
@@ -140,17 +108,15 @@ int yue_knn_neighbors(yue_ctx *c, int K, int32_t *nbr_out, int32_t *inter_out, i
     k->K = K;
     yue::KnnArgs a = base_args(c, k);
     a.cursor = k->cursor.p;
-    HIPCHK(hipEventRecord(k->ev[0], c->stream));
+    HIPCHK(k->ev[0].record(c->stream));
     hipLaunchKernelGGL(yue::k_knn_neighbors, dim3((unsigned)k->m), dim3(yue::kKnnThreads), 0, c->stream, a);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(k->ev[1], c->stream));
+    HIPCHK(k->ev[1].record(c->stream));
     if (nbr_out) HIPCHK(hipMemcpyAsync(nbr_out, k->nbr.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     if (inter_out) HIPCHK(hipMemcpyAsync(inter_out, k->inter.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     if (union_out) HIPCHK(hipMemcpyAsync(union_out, k->uni.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    float ms = 0.0f;
-    HIPCHK(hipEventElapsedTime(&ms, k->ev[0], k->ev[1]));
-    c->knn_ns = (int64_t)(1e6 * (double)ms);
+    HIPCHK(yue_host::elapsed(k->ev[0], k->ev[1], &c->knn_ns));
     return YUE_OK;
 }
 
@@ -171,19 +137,17 @@ int yue_knn_topn(yue_ctx *c, const int32_t *users, int64_t nu, int N, int32_t *i
     yue::KnnArgs a = base_args(c, k);
     a.users = k->users.p; a.N = N; a.exclude_own = 1;
     a.ids_out = k->ids.p; a.scores_out = k->scores.p; a.len_out = k->len.p; a.chunked_users = k->chunked.p;
-    HIPCHK(hipEventRecord(k->ev[0], c->stream));
+    HIPCHK(k->ev[0].record(c->stream));
     hipLaunchKernelGGL(yue::k_knn_topn, dim3((unsigned)nu), dim3(yue::kKnnThreads), 0, c->stream, a);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(k->ev[1], c->stream));
+    HIPCHK(k->ev[1].record(c->stream));
     int chunked = 0;
     HIPCHK(hipMemcpyAsync(ids_out, k->ids.p, (size_t)nu * N * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(scores_out, k->scores.p, (size_t)nu * N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(len_out, k->len.p, (size_t)nu * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(&chunked, k->chunked.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    float ms = 0.0f;
-    HIPCHK(hipEventElapsedTime(&ms, k->ev[0], k->ev[1]));
-    c->knn_ns = (int64_t)(1e6 * (double)ms);
+    HIPCHK(yue_host::elapsed(k->ev[0], k->ev[1], &c->knn_ns));
     c->knn_chunked_users = chunked;
     return YUE_OK;
 }
@@ -198,16 +162,14 @@ int yue_knn_predict(yue_ctx *c, int32_t user, int64_t cap, int32_t *items_out, d
     HIPCHK(k->scores.resize((size_t)k->n));
     yue::KnnArgs a = base_args(c, k);
     a.user = user; a.item_scores = k->scores.p;
-    HIPCHK(hipEventRecord(k->ev[0], c->stream));
+    HIPCHK(k->ev[0].record(c->stream));
     hipLaunchKernelGGL(yue::k_knn_predict_scores, dim3((unsigned)((k->n + yue::kKnnThreads - 1) / yue::kKnnThreads)), dim3(yue::kKnnThreads), 0, c->stream, a);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(k->ev[1], c->stream));
+    HIPCHK(k->ev[1].record(c->stream));
     std::vector<double> sc((size_t)k->n);
     HIPCHK(hipMemcpyAsync(sc.data(), k->scores.p, (size_t)k->n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    float ms = 0.0f;
-    HIPCHK(hipEventElapsedTime(&ms, k->ev[0], k->ev[1]));
-    c->knn_ns = (int64_t)(1e6 * (double)ms);
+    HIPCHK(yue_host::elapsed(k->ev[0], k->ev[1], &c->knn_ns));
     // the one-user list: the scored items by (score descending, item ascending)
     std::vector<int32_t> order;
     for (int64_t i = 0; i < k->n; ++i)

@@ -6,7 +6,7 @@
 
 using gcn::launch_product;
 using gcn::stamp;
-using gcn::upload;
+using yue_host::upload;
 using yue_host::fail;
 
 struct yue_lgcn {
@@ -23,13 +23,6 @@ struct yue_lgcn {
 namespace {
 
 enum { kForward = 0, kBatch = 1, kBackward = 2, kAdam = 3, kPhases = 4 };
-
-int lgcn_new(yue_ctx *c) {
-    if (c->lgcn) return YUE_OK;
-    HIPCHK(hipSetDevice(c->device));
-    c->lgcn = new yue_lgcn();
-    return YUE_OK;
-}
 
 // one side's lists: ptr[0] = 0, ascending ptr, ids strictly ascending within a row and below `other`, finite weights
 int check_side(const char *side, int64_t rows, int64_t other, const int64_t *ptr, const int32_t *ids, const float *w) {
@@ -51,7 +44,7 @@ int lgcn_ready(yue_ctx *c, yue_lgcn **out, int layers, const char *who) {
     if (!c->have_factors) return fail(YUE_ERR_ARG, std::string(who) + ": call yue_set_factors first (U, V)");
     if (c->k > yue::kLgcnMaxK) return fail(YUE_ERR_ARG, std::string(who) + ": needs k <= 128");
     if (layers < 1 || layers > 64) return fail(YUE_ERR_ARG, std::string(who) + ": needs 1 <= layers <= 64");
-    yue_lgcn *s = c->lgcn;
+    yue_lgcn *s = c->lgcn.get();
     if (!s || !s->have_graph) return fail(YUE_ERR_ARG, std::string(who) + ": call yue_lgcn_set_graph first");
     if (s->m != c->m || s->n != c->n)
         return fail(YUE_ERR_ARG, std::string(who) + ": the graph was set for " + std::to_string(s->m) + " users and " + std::to_string(s->n) +
@@ -117,20 +110,6 @@ int gradient(yue_ctx *c, yue_lgcn *s, int L, const int32_t *u, const int32_t *i,
 
 }  // namespace
 
-namespace yue_host {
-
-void lgcn_release(yue_ctx *c) {
-    yue_lgcn *s = c->lgcn;
-    if (!s) return;
-    s->A.release(); s->partial.release();
-    s->E.release(); s->ss.release(); s->F.release(); s->G.release(); s->gA.release(); s->gB.release();
-    s->batch.release(); s->timer.release();
-    delete s;
-    c->lgcn = nullptr;
-}
-
-}  // namespace yue_host
-
 extern "C" {
 
 int yue_lgcn_set_graph(yue_ctx *c, int64_t m, int64_t n, const int64_t *u_ptr, const int32_t *u_items, const float *u_w, const int64_t *i_ptr,
@@ -154,8 +133,8 @@ int yue_lgcn_set_graph(yue_ctx *c, int64_t m, int64_t n, const int64_t *u_ptr, c
             if (i_users[q] != u || i_w[q] != u_w[p])
                 return fail(YUE_ERR_ARG, "yue_lgcn_set_graph: the graph is not symmetric (user " + std::to_string(u) + ", item " + std::to_string(u_items[p]) + ")");
         }
-    if ((rc = lgcn_new(c))) return rc;
-    yue_lgcn *s = c->lgcn;
+    yue_lgcn *s = nullptr;
+    if ((rc = yue_host::state(c, c->lgcn, &s))) return rc;
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
     s->have_graph = false;

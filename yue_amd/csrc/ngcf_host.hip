@@ -8,7 +8,7 @@
 
 #include "ngcf_kernels.hpp"
 
-using gcn::upload;
+using yue_host::upload;
 using yue_host::fail;
 
 struct yue_ngcf {
@@ -37,13 +37,6 @@ struct Run {                                         // what one call propagates
     uint64_t seed, step;
 };
 
-int ngcf_new(yue_ctx *c) {
-    if (c->ngcf) return YUE_OK;
-    HIPCHK(hipSetDevice(c->device));
-    c->ngcf = new yue_ngcf();
-    return YUE_OK;
-}
-
 int stamp(yue_ctx *c, yue_ngcf *s, int phase) { return gcn::stamp(c, s->timer, phase); }
 
 int ngcf_ready(yue_ctx *c, yue_ngcf **out, int layers, double keep, const char *who) {
@@ -55,7 +48,7 @@ int ngcf_ready(yue_ctx *c, yue_ngcf **out, int layers, double keep, const char *
     if ((int64_t)(layers + 1) * c->k > yue::kNgcfMaxWidth)
         return fail(YUE_ERR_ARG, w + ": needs (layers + 1) k <= 256, the width the minibatch kernels and the scan take");
     if (!(keep > 0.0 && keep <= 1.0)) return fail(YUE_ERR_ARG, w + ": needs 0 < keep <= 1");
-    yue_ngcf *s = c->ngcf;
+    yue_ngcf *s = c->ngcf.get();
     if (!s || !s->have_graph) return fail(YUE_ERR_ARG, w + ": call yue_ngcf_set_graph first");
     if (s->m != c->m || s->n != c->n)
         return fail(YUE_ERR_ARG, w + ": the graph was set for " + std::to_string(s->m) + " users and " + std::to_string(s->n) + " items, the factors hold " +
@@ -182,22 +175,6 @@ Run make_run(int layers, int training, double keep, uint64_t seed, int64_t step)
 
 }  // namespace
 
-namespace yue_host {
-
-void ngcf_release(yue_ctx *c) {
-    yue_ngcf *s = c->ngcf;
-    if (!s) return;
-    s->A.release(); s->At.release(); s->partial.release();
-    s->W.release(); s->gW.release(); s->mW.release(); s->vW.release(); s->wpart.release();
-    s->E0.release(); s->S.release(); s->Z.release(); s->D.release(); s->ss.release(); s->F.release(); s->G.release();
-    s->gD.release(); s->gZ.release(); s->gS.release();
-    s->batch.release(); s->timer.release();
-    delete s;
-    c->ngcf = nullptr;
-}
-
-}  // namespace yue_host
-
 extern "C" {
 
 int yue_ngcf_set_graph(yue_ctx *c, int64_t m, int64_t n, const int64_t *ptr, const int32_t *col, const float *w) {
@@ -217,8 +194,8 @@ int yue_ngcf_set_graph(yue_ctx *c, int64_t m, int64_t n, const int64_t *ptr, con
             if (!std::isfinite(w[p])) return fail(YUE_ERR_ARG, "yue_ngcf_set_graph: row " + std::to_string(r) + ": weight not finite");
         }
     int rc;
-    if ((rc = ngcf_new(c))) return rc;
-    yue_ngcf *s = c->ngcf;
+    yue_ngcf *s = nullptr;
+    if ((rc = yue_host::state(c, c->ngcf, &s))) return rc;
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
     s->have_graph = false;
@@ -251,8 +228,8 @@ int yue_ngcf_set_weights(yue_ctx *c, int layers, int k, const float *W) {
     for (int64_t t = 0; t < count; ++t)
         if (!std::isfinite(W[t])) return fail(YUE_ERR_ARG, "yue_ngcf_set_weights: weight not finite");
     int rc;
-    if ((rc = ngcf_new(c))) return rc;
-    yue_ngcf *s = c->ngcf;
+    yue_ngcf *s = nullptr;
+    if ((rc = yue_host::state(c, c->ngcf, &s))) return rc;
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
     s->have_weights = false;
@@ -268,7 +245,7 @@ int yue_ngcf_set_weights(yue_ctx *c, int layers, int k, const float *W) {
 
 int yue_ngcf_get_weights(yue_ctx *c, float *W, float *mW, float *vW) {
     if (!c || !c->ngcf || !c->ngcf->have_weights) return fail(YUE_ERR_ARG, "yue_ngcf_get_weights: call yue_ngcf_set_weights first");
-    yue_ngcf *s = c->ngcf;
+    yue_ngcf *s = c->ngcf.get();
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
     const size_t bytes = (size_t)s->wl * 2 * s->wk * s->wk * sizeof(float);

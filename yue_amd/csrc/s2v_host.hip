@@ -8,6 +8,7 @@
 #include <numeric>
 
 using yue_host::fail;
+using yue_host::upload;
 
 namespace {
 
@@ -16,7 +17,6 @@ struct Schedule {
     int64_t count = 0, levels = 0;
     std::vector<int64_t> level_ptr;
     DevBuf<int32_t> a, b, order;
-    void release() { a.release(); b.release(); order.release(); }
 };
 
 }  // namespace
@@ -28,32 +28,23 @@ struct yue_s2v {
     Schedule steps, pairs;
     DevBuf<int32_t> cnt;
     DevBuf<float> sim32;
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    Event ev[2];
 };
 
 namespace {
 
+// the state for an entry point that takes the context's factors as X and Y
 int s2v_state(yue_ctx *c, yue_s2v **out, const char *who) {
     if (!c->have_factors) return fail(YUE_ERR_ARG, std::string(who) + ": call yue_set_factors first (X, Y)");
     if (c->k > yue::kS2vMaxK) return fail(YUE_ERR_ARG, std::string(who) + ": needs k <= 128");
-    if (!c->s2v) {
-        HIPCHK(hipSetDevice(c->device));
-        c->s2v = new yue_s2v();
-        for (auto &e : c->s2v->ev) HIPCHK(hipEventCreate(&e));
-    }
-    yue_s2v *s = c->s2v;
+    yue_s2v *s = nullptr;
+    const int rc = yue_host::state(c, c->s2v, &s);
+    if (rc) return rc;
     if (s->m != c->m || s->n != c->n) {          // other factors: nothing uploaded for the old shape survives
         s->m = c->m; s->n = c->n;
         s->have_state = false; s->steps.count = 0; s->steps.levels = 0; s->pairs.count = 0; s->pairs.levels = 0;
     }
     *out = s;
-    return YUE_OK;
-}
-
-template <typename T>
-int upload(DevBuf<T> &buf, const T *src, int64_t count) {
-    HIPCHK(buf.resize((size_t)std::max<int64_t>(count, 1)));
-    if (count > 0) HIPCHK(hipMemcpy(buf.p, src, (size_t)count * sizeof(T), hipMemcpyHostToDevice));
     return YUE_OK;
 }
 
@@ -111,16 +102,6 @@ int run_pass(yue_ctx *c, const Schedule &sch, yue::S2vArgs a) {
 
 namespace yue_host {
 
-void s2v_release(yue_ctx *c) {
-    yue_s2v *s = c->s2v;
-    if (!s) return;
-    s->Bu.release(); s->Bi.release(); s->bu0.release(); s->err2.release(); s->steps.release(); s->pairs.release();
-    s->cnt.release(); s->sim32.release();
-    for (auto &e : s->ev) if (e) (void)hipEventDestroy(e);
-    delete s;
-    c->s2v = nullptr;
-}
-
 // which: 0 the rating steps' levels, 1 the similarity pairs'
 int64_t s2v_levels(const yue_ctx *c, int which) { return !c->s2v ? 0 : which == 0 ? c->s2v->steps.levels : c->s2v->pairs.levels; }
 
@@ -143,7 +124,7 @@ int yue_s2v_set_state(yue_ctx *c, const double *Bu, const double *Bi) {
 
 int yue_s2v_get_state(yue_ctx *c, double *Bu, double *Bi) {
     if (!c) return fail(YUE_ERR_ARG, "yue_s2v_get_state: null context");
-    yue_s2v *s = c->s2v;
+    yue_s2v *s = c->s2v.get();
     if (!s || !s->have_state || s->m != c->m || s->n != c->n) return fail(YUE_ERR_ARG, "yue_s2v_get_state: call yue_s2v_set_state first");
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -207,17 +188,15 @@ int yue_s2v_epoch(yue_ctx *c, double lr, double regU, double regI, double regB, 
     a.t1 = s->pairs.a.p; a.t2 = s->pairs.b.p; a.sim32 = s->sim32.p;
     a.lr = lr; a.regB = regB; a.ru = (float)regU; a.ri = (float)regI; a.gm32 = (float)globalMean;
     a.coef32 = (float)(0.5 * alpha * lr);
-    HIPCHK(hipEventRecord(s->ev[0], c->stream));
+    HIPCHK(s->ev[0].record(c->stream));
     HIPCHK(hipMemcpyAsync(s->bu0.p, s->Bu.p, (size_t)s->m * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     a.err2 = s->err2.p;
     if ((rc = run_pass<false>(c, s->steps, a))) return rc;
     a.err2 = s->err2.p + T;
     if ((rc = run_pass<true>(c, s->pairs, a))) return rc;
-    HIPCHK(hipEventRecord(s->ev[1], c->stream));
+    HIPCHK(s->ev[1].record(c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    float ms = 0.0f;
-    HIPCHK(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
-    c->s2v_ns = (int64_t)(1e6 * (double)ms);
+    HIPCHK(yue_host::elapsed(s->ev[0], s->ev[1], &c->s2v_ns));
     if (err2_steps && T > 0) HIPCHK(hipMemcpy(err2_steps, s->err2.p, (size_t)T * sizeof(double), hipMemcpyDeviceToHost));
     if (err2_pairs && Pn > 0) HIPCHK(hipMemcpy(err2_pairs, s->err2.p + T, (size_t)Pn * sizeof(double), hipMemcpyDeviceToHost));
     return YUE_OK;

@@ -211,9 +211,7 @@ int yue_topn_scan(yue_ctx *c, const int32_t *users, int64_t nu, int N, const int
     std::vector<unsigned long long> wslots(4 * yue::kWorkSlots, 0ull);
     HIPCHK(hipMemcpyAsync(wslots.data(), c->s_work.p, wslots.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, t0, t1));
-    c->scan_ms = ms;
+    HIPCHK(yue_host::elapsed(t0, t1, &c->scan_ms));
     unsigned long long work[4] = {0, 0, 0, 0};
     for (int q = 0; q < yue::kWorkSlots; ++q) for (int z = 0; z < 4; ++z) work[z] += wslots[(size_t)4 * q + z];
     c->scan_events = (int64_t)work[1];

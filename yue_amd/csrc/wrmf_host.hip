@@ -26,38 +26,10 @@ struct yue_wrmf {
     yue_wrmf_side side[2];
     DevBuf<double> gram_part, G, ws, row_loss, loss;
     DevBuf<int> status;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    Event ev[4];
 };
 
-namespace yue_host {
-
-void wrmf_release(yue_ctx *c) {
-    yue_wrmf *w = c->wrmf;
-    if (!w) return;
-    for (auto &s : w->side) {
-        s.ptr.release(); s.cptr.release(); s.cbeg.release(); s.cend.release();
-        s.idx.release(); s.cnt.release(); s.sched.release(); s.cpos.release();
-    }
-    w->gram_part.release(); w->G.release(); w->ws.release(); w->row_loss.release(); w->loss.release(); w->status.release();
-    for (auto &e : w->ev) if (e) (void)hipEventDestroy(e);
-    delete w;
-    c->wrmf = nullptr;
-}
-
-}  // namespace yue_host
-
 namespace {
-
-int wrmf_state(yue_ctx *c, yue_wrmf **out) {
-    if (!c->wrmf) {
-        HIPCHK(hipSetDevice(c->device));
-        yue_wrmf *w = new yue_wrmf();
-        c->wrmf = w;
-        for (auto &e : w->ev) HIPCHK(hipEventCreate(&e));
-    }
-    *out = c->wrmf;
-    return YUE_OK;
-}
 
 // checks one direction's CSR: ptr[rows+1] from 0 to nnz, ids sorted-unique in [0, ids_bound), counts >= 1
 int check_csr(const int64_t *ptr, const int32_t *ids, const int32_t *cnt, int64_t rows, int64_t ids_bound, int64_t nnz, const char *what) {
@@ -122,7 +94,7 @@ int upload_side(int64_t long_pairs, yue_wrmf_side &s, const int64_t *ptr, const 
 namespace yue_host {
 
 bool wrmf_pairs_view(const yue_ctx *c, int side, WrmfPairsView *v) {
-    const yue_wrmf *w = c->wrmf;
+    const yue_wrmf *w = c->wrmf.get();
     if (!w || w->m == 0 || w->m != c->m || w->n != c->n) return false;
     const yue_wrmf_side &s = w->side[side];
     v->ptr = s.ptr.p; v->cptr = s.cptr.p; v->cbeg = s.cbeg.p; v->cend = s.cend.p;
@@ -133,7 +105,7 @@ bool wrmf_pairs_view(const yue_ctx *c, int side, WrmfPairsView *v) {
 }
 
 int wrmf_gram(yue_ctx *c, int side, const double **G) {
-    yue_wrmf *w = c->wrmf;
+    yue_wrmf *w = c->wrmf.get();
     if (!w || w->m == 0 || w->m != c->m || w->n != c->n) return fail(YUE_ERR_ARG, "wrmf_gram: call yue_wrmf_set_pairs first");
     const float *F = side == 0 ? c->Q.p : c->P.p;
     const int64_t nf = side == 0 ? c->n : c->m;
@@ -171,7 +143,7 @@ int yue_wrmf_set_pairs(yue_ctx *c, const int64_t *u_ptr, const int32_t *u_items,
     }
     HIPCHK(hipSetDevice(c->device));
     yue_wrmf *w = nullptr;
-    if ((rc = wrmf_state(c, &w))) return rc;
+    if ((rc = yue_host::state(c, c->wrmf, &w))) return rc;
     w->m = 0;                                                  // invalid until both sides are up
     if ((rc = upload_side(c->opt_wrmf_long_pairs, w->side[0], u_ptr, u_items, u_counts, m, nnz))) return rc;
     if ((rc = upload_side(c->opt_wrmf_long_pairs, w->side[1], i_ptr, i_users, i_counts, n, nnz))) return rc;
@@ -189,7 +161,7 @@ int yue_wrmf_set_pairs(yue_ctx *c, const int64_t *u_ptr, const int32_t *u_items,
 
 int yue_wrmf_half_sweep(yue_ctx *c, int side, double alpha, double reg, double *loss_out) {
     if (!c || !c->have_factors) return fail(YUE_ERR_ARG, "yue_wrmf_half_sweep: no factors uploaded");
-    yue_wrmf *w = c->wrmf;
+    yue_wrmf *w = c->wrmf.get();
     if (!w || w->m == 0) return fail(YUE_ERR_ARG, "yue_wrmf_half_sweep: call yue_wrmf_set_pairs first");
     if (w->m != c->m || w->n != c->n) return fail(YUE_ERR_ARG, "yue_wrmf_half_sweep: the factors' shape changed since yue_wrmf_set_pairs");
     if (side != 0 && side != 1) return fail(YUE_ERR_ARG, "yue_wrmf_half_sweep: side must be 0 (user rows) or 1 (item rows)");
@@ -209,28 +181,25 @@ int yue_wrmf_half_sweep(yue_ctx *c, int side, double alpha, double reg, double *
     a.want_loss = side == 0 ? 1 : 0; a.row_loss = w->row_loss.p; a.status = w->status.p;
     const int none = INT_MAX;
     HIPCHK(hipMemcpyAsync(w->status.p, &none, sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipEventRecord(w->ev[0], c->stream));
+    HIPCHK(w->ev[0].record(c->stream));
     int rc = yue_host::wrmf_gram(c, side, &a.G);                // F^T F of the fixed side, rounded to fp32 once
     if (rc) return rc;
-    HIPCHK(hipEventRecord(w->ev[1], c->stream));
+    HIPCHK(w->ev[1].record(c->stream));
     if (s.chunks > 0) hipLaunchKernelGGL(yue::k_wrmf_chunk, dim3((unsigned)s.chunks), dim3(yue::kWrmfThreads), 0, c->stream, a);
-    HIPCHK(hipEventRecord(w->ev[2], c->stream));
+    HIPCHK(w->ev[2].record(c->stream));
     const int lds = yue::wrmf_dyn_lds(k);
     HIPCHK(hipFuncSetAttribute((const void *)yue::k_wrmf_solve, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     hipLaunchKernelGGL(yue::k_wrmf_solve, dim3((unsigned)s.rows), dim3(yue::kWrmfThreads), lds, c->stream, a);
     if (side == 0) hipLaunchKernelGGL(yue::k_wrmf_loss_sum, dim3(1), dim3(yue::kWrmfThreads), 0, c->stream, (const double *)w->row_loss.p, s.rows, w->loss.p);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(w->ev[3], c->stream));
+    HIPCHK(w->ev[3].record(c->stream));
     int status = INT_MAX;
     double loss = 0.0;
     HIPCHK(hipMemcpyAsync(&status, w->status.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     if (side == 0) HIPCHK(hipMemcpyAsync(&loss, w->loss.p, sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    float ms_all = 0.0f, ms_long = 0.0f;
-    HIPCHK(hipEventElapsedTime(&ms_all, w->ev[0], w->ev[3]));
-    HIPCHK(hipEventElapsedTime(&ms_long, w->ev[1], w->ev[2]));
-    c->wrmf_ns[0] = (int64_t)(1e6 * (double)ms_all);
-    c->wrmf_ns[1] = (int64_t)(1e6 * (double)ms_long);
+    HIPCHK(yue_host::elapsed(w->ev[0], w->ev[3], &c->wrmf_ns[0]));
+    HIPCHK(yue_host::elapsed(w->ev[1], w->ev[2], &c->wrmf_ns[1]));
     if (status != INT_MAX)
         return fail(YUE_ERR_ARG, std::string("yue_wrmf_half_sweep: non-positive pivot in the Cholesky factorisation of ") + (side == 0 ? "user" : "item") +
                                      " row " + std::to_string(status) + " (A = F^T F + C + reg*I is not positive definite: raise reg)");
