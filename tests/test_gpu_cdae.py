@@ -189,9 +189,9 @@ def test_refusals(dev):
     bad = list(users); bad[2] = c['m']
     assert 'user out of range' in refused(dev.cdae_grad, bad, sptr, sitems, co, seed, step, reg)
     bad = sitems.copy(); bad[1] = bad[0]
-    assert 'ascending and distinct' in refused(dev.cdae_grad, users, sptr, bad, co, seed, step, reg)
+    assert 'yue_cdae_grad: sample rows must be sorted and unique (row 0)' in refused(dev.cdae_grad, users, sptr, bad, co, seed, step, reg)
     bad = sitems.copy(); bad[int(sptr[1]) - 1] = c['n']
-    assert 'item out of range' in refused(dev.cdae_forward, users, sptr, bad, co, seed, step, reg)
+    assert 'yue_cdae_forward: sample id out of range (row 0)' in refused(dev.cdae_forward, users, sptr, bad, co, seed, step, reg)
     refused(dev.cdae_forward, users[:0], sptr[:1], sitems, co, seed, step, reg)              # B < 1
     refused(dev.cdae_forward, users, sptr, sitems, 0.0, seed, step, reg)
     refused(dev.cdae_forward, users, sptr, sitems, 1.5, seed, step, reg)
@@ -203,7 +203,7 @@ def test_refusals(dev):
     refused(dev.cdae_set_params, p['U'], W, p['Wd'], p['b'], p['bd'])
     ptr, items, cnt = c['data']
     two = items.copy(); two[int(ptr[1]) + 1] = two[int(ptr[1])]
-    assert 'ascending and distinct' in refused(dev.cdae_set_data, c['m'], c['n'], ptr, two, cnt)
+    assert 'yue_cdae_set_data: user-major rows must be sorted and unique (row 1)' in refused(dev.cdae_set_data, c['m'], c['n'], ptr, two, cnt)
     # after the refusals the good state still answers
     loss, g = dev.cdae_grad(*batch(c))
     assert abs(loss - c['loss']) / abs(c['loss']) <= cc.bound(c, 'loss')
@@ -217,3 +217,24 @@ def test_refusals(dev):
         assert 'set_params first' in refused(fresh.cdae_load_factors)
     finally:
         fresh.close()
+
+
+def test_the_user_lists_are_checked_against_their_own_bound():
+    # m = 5 users, n = 3 items: a bound or a row count swapped at a call site of the shared check shows
+    from helpers import row_list_cases as rl
+    from yue_amd._shim import Device, YueHipError
+    d = Device(0, raise_errors=True)
+    try:
+        ones = np.ones(rl.NNZ, np.int32)
+
+        def upload(ptr, items, counts=ones):
+            d.cdae_set_data(rl.M, rl.N, ptr, items, counts)
+        base = {'ptr': rl.U_PTR.copy(), 'items': rl.U_ITEMS.copy()}
+        rl.check_wiring('yue_cdae_set_data', upload, base, [('ptr', 'items', rl.N, True)])
+        for bad in (0, 1 << 24):
+            counts = ones.copy(); counts[3] = bad
+            with pytest.raises(YueHipError, match=r'yue_cdae_set_data: user-major row 2: a count must be 1 \.\. 2\^24 - 1'):
+                upload(counts=counts, **base)
+            upload(**base)
+    finally:
+        d.close()

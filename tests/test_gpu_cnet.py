@@ -271,3 +271,19 @@ def test_plugin_without_net_option_is_unchanged(tmp_path, capsys):
     out = capsys.readouterr().out
     assert out == 'CUNE: no -friends file: the user-network stage (gensim) is not part of this build; every user takes the plain step.\n'
     assert len(rec.IPositiveSet) == 0 and not hasattr(rec, 'topKSim')
+
+
+def test_pair_lists_are_checked_against_their_own_bounds():
+    # m = 5 users, n = 3 items: a bound or a row count swapped at a call site of the shared check shows
+    from helpers import row_list_cases as rl
+    from yue_amd._shim import Device, YueHipError
+    d = Device(0, raise_errors=True)
+    try:
+        def upload(u_ptr, u_items, i_ptr, i_users):
+            d.cnet_set_pairs(rl.M, rl.N, u_ptr, u_items, i_ptr, i_users)
+        rl.check_wiring('yue_cnet_set_pairs', upload, rl.lists(), [('u_ptr', 'u_items', rl.N, True), ('i_ptr', 'i_users', rl.M, True)])
+        with pytest.raises(YueHipError, match='yue_cnet_set_pairs: .*not the transpose'):
+            upload(**dict(rl.lists(), i_users=rl.not_the_transpose()))
+        upload(**rl.lists())
+    finally:
+        d.close()

@@ -260,7 +260,7 @@ def test_refusals_leave_the_context_usable(dev):
     r = int(np.flatnonzero(np.diff(sp[0]) >= 2)[0])
     a = int(sp[0][r])
     idx2[a], idx2[a + 1] = idx2[a + 1], idx2[a]
-    with pytest.raises(YueHipError, match='not ascending'):
+    with pytest.raises(YueHipError, match='yue_cof_set_sppmi: SPPMI rows must be sorted and unique .row %d.' % r):
         dev.cof_set_sppmi(sp[0], idx2, sp[2])
     dptr = np.zeros(n + 1, np.int64)
     dptr[i + 1:] = 1
@@ -350,3 +350,24 @@ def test_full_size_cooccurrence_and_one_iteration(dev):
     G, w, c = dev.cof_get_state()
     assert np.isfinite(loss) and np.isfinite(X).all() and np.isfinite(Y).all() and np.isfinite(G).all() and np.isfinite(w).all() and np.isfinite(c).all()
     assert dev.get_option('cof_levels') >= 1
+
+
+def test_the_sppmi_rows_are_checked_against_their_own_bound():
+    # m = 5 users, n = 3 items; the SPPMI is n x n: every pair of different items, value 1
+    from helpers import row_list_cases as rl
+    from yue_amd._shim import Device, YueHipError
+    d = Device(0, raise_errors=True)
+    try:
+        d.set_factors(np.zeros((rl.M, 8), np.float32), np.zeros((rl.N, 8), np.float32))
+        base = {'ptr': np.array([0, 2, 4, 6], np.int64), 'idx': np.array([1, 2, 0, 2, 0, 1], np.int32)}
+        ones = np.ones(6)
+
+        def upload(ptr, idx, val=ones):
+            d.cof_set_sppmi(ptr, idx, val)
+        rl.check_wiring('yue_cof_set_sppmi', upload, base, [('ptr', 'idx', rl.N, True)])
+        inf = ones.copy(); inf[5] = np.inf
+        with pytest.raises(YueHipError, match='yue_cof_set_sppmi: SPPMI row 2: holds a value that is not finite'):
+            upload(val=inf, **base)
+        upload(**base)
+    finally:
+        d.close()

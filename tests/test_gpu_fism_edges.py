@@ -245,6 +245,9 @@ def test_refusals_change_nothing(dev):
     down = ptr.copy()
     down[3] = down[2] - 1
     both(ptr_=down, words='non-decreasing')
+    far = ptr.copy()
+    far[1] = 10 ** 6                                             # row 0 alone looks fine; its ids would lie far past ev_i
+    both(ptr_=far, words='non-decreasing')
     for bad in (-1, n):
         ev = ev_i.copy()
         ev[3] = bad
@@ -280,3 +283,11 @@ def test_refusals_change_nothing(dev):
     d = distances((half, None, P, Q, Bi, None), fc.oracle(name, 5))
     print('after the refusals, rounds of 5 form %d: P %.3g Q %.3g Bi %.3g half %.3g' % ((dev.get_option('fism_last_form'),) + d))
     assert max(d) < 1e-6 and dev.get_option('fism_last_form') == 2
+    # the last item, n - 1, is an event's item like any other (no draw names its own event's item: the case's events stay below 25)
+    ev = ev_i.copy()
+    ev[3] = n - 1
+    assert ev_i.max() < n - 2
+    ng = np.where(negs == n - 1, n - 2, negs).astype(np.int32)
+    dev.fism_set_model(c['P0'], c['Q0'], c['B0'])
+    assert np.isfinite(dev.fism_epoch(ptr, ev, ng, rho, coef, c['lr'], fc.REG_I, fc.REG_B)).all()
+    assert np.isfinite(dev.fism_rounds(ptr, ev, ng, rho, coef, 4, c['lr'], fc.REG_I, fc.REG_B)).all()

@@ -141,3 +141,23 @@ def test_csr_data_set_gives_the_same_lists(tmp_path, capsys):
     assert sorted(expect) == list(got['users'])
     for t, u in enumerate(got['users']):
         assert list(got['ids'][t, :got['lens'][t]]) == expect[int(u)], u
+
+
+def test_the_four_lists_are_checked_against_their_own_bounds():
+    # m = 5 users, n = 3 items: a bound or a row count swapped at a call site of the shared check shows
+    from helpers import row_list_cases as rl
+    from yue_amd._shim import Device, YueHipError
+    from yue_amd.recommender.cf.IPF import ipf_graph
+    d = Device(0, raise_errors=True)
+    try:
+        g = ipf_graph(rl.U_PTR, rl.U_ITEMS, rl.N, 1.0, 0.7, 0.3)
+        rl.check_wiring('yue_ipf_set_graph', lambda **lists: d.ipf_set_graph(lists), g,
+                        [('u_ptr', 'u_items', rl.N, False), ('s_ptr', 's_items', rl.N, False), ('hu_ptr', 'hu_users', rl.M, False), ('hs_ptr', 'hs_users', rl.M, False)])
+        for key, words in (('u_items', 'user lists'), ('s_items', 'session lists'), ('hu_users', 'item2user lists'), ('hs_users', 'item2session lists')):
+            twice = g[key].copy(); twice[-1] = twice[-2]                 # the last row of each holds two ids
+            with pytest.raises(YueHipError, match='yue_ipf_set_graph: %s rows must hold distinct ids' % words):
+                d.ipf_set_graph(dict(g, **{key: twice}))
+            unsorted = g[key].copy(); unsorted[0], unsorted[1] = unsorted[1], unsorted[0]
+            d.ipf_set_graph(dict(g, **{key: unsorted}))                  # any order is in order here
+    finally:
+        d.close()

@@ -151,3 +151,22 @@ def test_buffers_are_reused_after_a_graph_of_another_shape(dev):
     check_case(dev, small)                                       # fewer rows, smaller k, no hubs: every buffer is larger than needed
     assert dev.get_option('lgcn_last_hubs') == 0
     check_case(dev, big)
+
+
+def test_graph_lists_are_checked_against_their_own_bounds():
+    # m = 5 users, n = 3 items: a bound or a row count swapped at a call site of the shared check shows
+    from helpers import row_list_cases as rl
+    from yue_amd._shim import Device, YueHipError
+    d = Device(0, raise_errors=True)
+    try:
+        w = np.full(rl.NNZ, 0.5, np.float32)
+
+        def upload(u_ptr, u_items, i_ptr, i_users, i_w=w):
+            d.lgcn_set_graph(rl.M, rl.N, u_ptr, u_items, w, i_ptr, i_users, i_w)
+        rl.check_wiring('yue_lgcn_set_graph', upload, rl.lists(), [('u_ptr', 'u_items', rl.N, True), ('i_ptr', 'i_users', rl.M, True)])
+        nan = w.copy(); nan[rl.NNZ - 1] = np.nan
+        with pytest.raises(YueHipError, match='yue_lgcn_set_graph: item-side row 2: weight not finite'):
+            upload(**dict(rl.lists(), i_w=nan))
+        upload(**rl.lists())
+    finally:
+        d.close()

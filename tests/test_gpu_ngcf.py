@@ -206,3 +206,23 @@ def test_lightgcn_still_gives_its_result_after_ngcf_calls(dev):
     loss, gU, gV = dev.lgcn_grad(lg['layers'], lg['u'], lg['i'], lg['j'], lc.REG)
     assert nl.rel(gU, lg['gU']) <= 4 * lg['d32']['gU'] and nl.rel(gV, lg['gV']) <= 4 * lg['d32']['gV']
     assert abs(loss - lg['loss']) / abs(lg['loss']) <= 4 * lg['d32']['loss']
+
+
+def test_the_graph_is_checked_against_its_own_bound():
+    # m = 5 users, n = 3 items, the (m + n)-row graph of both directions
+    from helpers import row_list_cases as rl
+    from yue_amd._shim import Device, YueHipError
+    d = Device(0, raise_errors=True)
+    try:
+        base = {'ptr': np.concatenate([rl.U_PTR, rl.NNZ + rl.I_PTR[1:]]), 'col': np.concatenate([rl.M + rl.U_ITEMS, rl.I_USERS]).astype(np.int32)}
+        w = np.full(2 * rl.NNZ, 0.5, np.float32)
+
+        def upload(ptr, col, w=w):
+            d.ngcf_set_graph(rl.M, rl.N, ptr, col, w)
+        rl.check_wiring('yue_ngcf_set_graph', upload, base, [('ptr', 'col', rl.M + rl.N, True)])
+        inf = w.copy(); inf[2] = np.inf
+        with pytest.raises(YueHipError, match='yue_ngcf_set_graph: graph row 1: weight not finite'):
+            upload(w=inf, **base)
+        upload(**base)
+    finally:
+        d.close()

@@ -725,3 +725,22 @@ def test_every_round_kernel_instance_matches_the_oracle(orc, k, tpw):
         assert dev.get_option('round_last_user_seq') == _SEQ[0]
         assert rel_err(P, P1) < TOL and rel_err(Q, Q1) < TOL and abs(nll - nll_1) <= 1e-9 * abs(nll_1)
     dev.close()
+
+
+def test_interaction_and_event_lists_are_checked_against_their_own_bound():
+    # m = 5 users, n = 3 items: a bound or a row count swapped at a call site of the shared check shows
+    from helpers import row_list_cases as rl
+    from yue_amd._shim import Device, YueHipError
+    d = Device(0, raise_errors=True)
+    try:
+        d.set_factors(np.zeros((rl.M, 8), np.float32), np.zeros((rl.N, 8), np.float32))
+        base = {'indptr': rl.U_PTR.copy(), 'indices': rl.U_ITEMS.copy(), 'ev_ptr': rl.U_PTR.copy(), 'ev_i': rl.U_ITEMS.copy()}
+        rl.check_wiring('yue_set_interactions', d.set_interactions, base, [('indptr', 'indices', rl.N, True), ('ev_ptr', 'ev_i', rl.N, False)])
+        d.set_interactions(**dict(base, ev_i=rl.U_ITEMS[::-1].copy()))       # events come in any order, repeats included
+        d.set_interactions(**dict(base, ev_i=np.full(rl.NNZ, rl.N - 1, np.int32)))
+        every = {'indptr': np.array([0, 3, 3, 3, 3, 3], np.int64), 'indices': np.arange(3, dtype=np.int32)}
+        with pytest.raises(YueHipError, match='yue_set_interactions: a user listened to every item'):
+            d.set_interactions(**dict(base, **every))
+        d.set_interactions(**base)
+    finally:
+        d.close()

@@ -203,3 +203,21 @@ def test_csr_data_set_gives_the_same_lists(tmp_path, capsys):
         assert a.split(':')[0] == b.split(':')[0]
         if ':' in a:
             assert abs(float(a.split(':')[1]) - float(b.split(':')[1])) <= 1e-12
+
+
+def test_pair_lists_are_checked_against_their_own_bounds():
+    # m = 5 users, n = 3 items: a bound or a row count swapped at a call site of the shared check shows
+    from helpers import row_list_cases as rl
+    from yue_amd._shim import Device, YueHipError
+    d = Device(0, raise_errors=True)
+    try:
+        ones = np.ones(rl.NNZ, np.int32)
+
+        def upload(u_ptr, u_items, i_ptr, i_users):
+            d.knn_set_pairs(rl.M, rl.N, u_ptr, u_items, ones, i_ptr, i_users)
+        rl.check_wiring('yue_knn_set_pairs', upload, rl.lists(), [('u_ptr', 'u_items', rl.N, True), ('i_ptr', 'i_users', rl.M, True)])
+        with pytest.raises(YueHipError, match='yue_knn_set_pairs: .*not the transpose'):
+            upload(**dict(rl.lists(), i_users=rl.not_the_transpose()))
+        upload(**rl.lists())
+    finally:
+        d.close()

@@ -264,3 +264,28 @@ def test_saved_model_round_trip(tmp_path, capsys):
     again.isLoadModel = True
     assert again.execute() == first
     assert again.X.dtype == np.float32 and np.array_equal(again.X, rec.X) and np.array_equal(again.Y, rec.Y)
+
+
+def test_pair_lists_are_checked_against_their_own_bounds():
+    # m = 5 users, n = 3 items: a bound or a row count swapped at a call site of the shared check shows
+    from helpers import row_list_cases as rl
+    from yue_amd._shim import Device, YueHipError
+    d = Device(0, raise_errors=True)
+    try:
+        d.set_factors(np.zeros((rl.M, 8), np.float32), np.zeros((rl.N, 8), np.float32))
+        ones = np.ones(rl.NNZ, np.int32)
+
+        def upload(u_ptr, u_items, i_ptr, i_users, i_counts=ones):
+            d.wrmf_set_pairs(u_ptr, u_items, ones, i_ptr, i_users, i_counts)
+        rl.check_wiring('yue_wrmf_set_pairs', upload, rl.lists(), [('u_ptr', 'u_items', rl.N, True), ('i_ptr', 'i_users', rl.M, True)])
+        twos = ones.copy(); twos[4] = 2
+        for change in ({'i_users': rl.not_the_transpose()}, {'i_counts': twos}):     # another pair; the same pairs, another count
+            with pytest.raises(YueHipError, match='yue_wrmf_set_pairs: .*not the transpose'):
+                upload(**dict(rl.lists(), **change))
+            upload(**rl.lists())
+        zero = ones.copy(); zero[rl.NNZ - 1] = 0
+        with pytest.raises(YueHipError, match='yue_wrmf_set_pairs: item-major row 2: counts must be >= 1'):
+            upload(**dict(rl.lists(), i_counts=zero))
+        upload(**rl.lists())
+    finally:
+        d.close()

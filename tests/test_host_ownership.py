@@ -49,3 +49,13 @@ def test_upload_and_download_are_defined_once():
         definition = re.compile(r'^(?:inline\s+)?int\s+%s\s*\(' % name, re.M)
         counts = {f: len(definition.findall(text)) for f, text in src.items() if definition.search(text)}
         assert counts == {OWNER: overloads}, (name, counts)
+
+
+def test_row_lists_are_checked_in_one_place():
+    # the hand-written row-list checks are gone for good, and the transpose walk is written once
+    src = sources()
+    definition = re.compile(r'\b(check_csr|check_lists|check_side|fism_check_rows)\s*\([^;{)]*\)\s*\{')
+    found = [(name, m.group(1)) for name, text in src.items() if name != 'input_checks.hpp' for m in definition.finditer(text)]
+    assert not found, found
+    assert re.search(r'\bint\s+check_rows\s*\(', src['input_checks.hpp'])
+    assert [name for name, text in src.items() if 'not the transpose' in text] == ['input_checks.hpp']

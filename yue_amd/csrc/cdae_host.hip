@@ -119,19 +119,12 @@ yue::CdaeParts dev_parts(const yue_cdae *s, const PartsAt &a) {
 int prepare(yue_ctx *c, yue_cdae *s, const int32_t *users, int64_t B, const int64_t *sptr, const int32_t *sitems, const char *who) {
     const std::string w(who);
     if (B < 1 || B >= (1ll << 24) || !users || !sptr) return fail(YUE_ERR_ARG, w + ": needs 1 <= B < 2^24, the users and the sample pointers");
-    if (sptr[0] != 0) return fail(YUE_ERR_ARG, w + ": sample_ptr[0] must be 0");
-    for (int64_t b = 0; b < B; ++b) {
+    for (int64_t b = 0; b < B; ++b)
         if (users[b] < 0 || users[b] >= s->m) return fail(YUE_ERR_ARG, w + ": slot " + std::to_string(b) + ": user out of range");
-        if (sptr[b + 1] < sptr[b]) return fail(YUE_ERR_ARG, w + ": sample_ptr must ascend (slot " + std::to_string(b) + ")");
-    }
     const int64_t S = sptr[B];
     if (S >= (1ll << 31)) return fail(YUE_ERR_ARG, w + ": needs fewer than 2^31 sampled entries");
-    if (S > 0 && !sitems) return fail(YUE_ERR_ARG, w + ": null sample_items");
-    for (int64_t b = 0; b < B; ++b)
-        for (int64_t p = sptr[b]; p < sptr[b + 1]; ++p) {
-            if (sitems[p] < 0 || sitems[p] >= s->n) return fail(YUE_ERR_ARG, w + ": slot " + std::to_string(b) + ": item out of range");
-            if (p > sptr[b] && sitems[p] <= sitems[p - 1]) return fail(YUE_ERR_ARG, w + ": slot " + std::to_string(b) + ": items must be ascending and distinct");
-        }
+    int rc = check_rows(w + ": sample", sptr, B, sitems, s->n, yue_host::kNoTotal, Order::ascending);
+    if (rc) return rc;
     const int64_t hub = c->opt_cdae_hub, n = s->n;
     s->B = B; s->S = S;
     // encoder rows and their input entries
@@ -223,7 +216,6 @@ int prepare(yue_ctx *c, yue_cdae *s, const int32_t *users, int64_t B, const int6
     s->a_enc = pack_parts(pk, s->enc); s->a_dec = pack_parts(pk, s->seg_dec); s->a_ie = pack_parts(pk, s->seg_enc);
     s->a_usr = pack_parts(pk, s->seg_usr); s->a_all = pack_parts(pk, s->seg_all);
     HIPCHK(hipStreamSynchronize(c->stream));             // (the blocking upload below overwrites what an earlier call's kernels read)
-    int rc;
     if ((rc = upload(s->idx, pk.h.data(), (int64_t)pk.h.size()))) return rc;
     const size_t h = (size_t)s->h, one = 1;
     const int64_t partials = std::max(std::max(s->enc.partials, s->seg_dec.partials), std::max(std::max(s->seg_enc.partials, s->seg_usr.partials), s->seg_all.partials));
@@ -372,19 +364,12 @@ extern "C" {
 int yue_cdae_set_data(yue_ctx *c, int64_t m, int64_t n, const int64_t *ptr, const int32_t *items, const int32_t *counts) {
     if (!c || !ptr) return fail(YUE_ERR_ARG, "yue_cdae_set_data: null argument");
     if (m <= 0 || n <= 0 || m >= (1ll << 31) || n >= (1ll << 31)) return fail(YUE_ERR_ARG, "yue_cdae_set_data: need 0 < m, n < 2^31");
-    if (ptr[0] != 0) return fail(YUE_ERR_ARG, "yue_cdae_set_data: ptr[0] must be 0");
-    for (int64_t u = 0; u < m; ++u)
-        if (ptr[u + 1] < ptr[u]) return fail(YUE_ERR_ARG, "yue_cdae_set_data: ptr must ascend (user " + std::to_string(u) + ")");
     const int64_t nnz = ptr[m];
     if (nnz >= (1ll << 31)) return fail(YUE_ERR_ARG, "yue_cdae_set_data: needs fewer than 2^31 pairs");
     if (nnz > 0 && (!items || !counts)) return fail(YUE_ERR_ARG, "yue_cdae_set_data: null argument");
-    for (int64_t u = 0; u < m; ++u)
-        for (int64_t p = ptr[u]; p < ptr[u + 1]; ++p) {
-            if (items[p] < 0 || items[p] >= n) return fail(YUE_ERR_ARG, "yue_cdae_set_data: user " + std::to_string(u) + ": item out of range");
-            if (p > ptr[u] && items[p] <= items[p - 1]) return fail(YUE_ERR_ARG, "yue_cdae_set_data: user " + std::to_string(u) + ": items must be ascending and distinct");
-            if (counts[p] < 1 || counts[p] >= (1 << 24)) return fail(YUE_ERR_ARG, "yue_cdae_set_data: user " + std::to_string(u) + ": a count must be 1 .. 2^24 - 1");
-        }
-    int rc;
+    int rc = check_rows("yue_cdae_set_data: user-major", ptr, m, items, n, yue_host::kNoTotal, Order::ascending, yue_host::kNoLimit,
+                        [&](int64_t, int64_t p) { return counts[p] < 1 || counts[p] >= (1 << 24) ? "a count must be 1 .. 2^24 - 1" : nullptr; });
+    if (rc) return rc;
     yue_cdae *s = nullptr;
     if ((rc = yue_host::state(c, c->cdae, &s))) return rc;
     HIPCHK(hipSetDevice(c->device));

@@ -41,20 +41,6 @@ namespace {
 
 constexpr int kDefaultRoundWalks = 64;       // chosen by the planted-groups quality test
 
-// ptr[rows + 1] from 0 to nnz, ids sorted-unique in [0, bound)
-int check_csr(const int64_t *ptr, const int32_t *ids, int64_t rows, int64_t bound, int64_t nnz, const char *what) {
-    const std::string at = std::string("yue_cnet_set_pairs: ") + what;
-    if (!ptr || (nnz > 0 && !ids)) return fail(YUE_ERR_ARG, at + ": null array");
-    if (ptr[0] != 0 || ptr[rows] != nnz) return fail(YUE_ERR_ARG, at + " pointer must run from 0 to nnz");
-    for (int64_t r = 0; r < rows; ++r) {
-        if (ptr[r + 1] < ptr[r]) return fail(YUE_ERR_ARG, at + " pointer must be non-decreasing");
-        for (int64_t e = ptr[r]; e < ptr[r + 1]; ++e)
-            if (ids[e] < 0 || ids[e] >= bound || (e > ptr[r] && ids[e] <= ids[e - 1]))
-                return fail(YUE_ERR_ARG, at + " rows must hold sorted, unique ids in range");
-    }
-    return YUE_OK;
-}
-
 int stop_clock(yue_ctx *c, yue_cnet *k) {
     HIPCHK(k->ev[1].record(c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -73,19 +59,11 @@ int yue_cnet_set_pairs(yue_ctx *c, int64_t m, int64_t n, const int64_t *u_ptr, c
                        const int32_t *i_users, int64_t nnz) {
     if (!c) return fail(YUE_ERR_ARG, "yue_cnet_set_pairs: null context");
     if (m < 1 || n < 1 || nnz < 0 || m >= INT32_MAX || n >= INT32_MAX) return fail(YUE_ERR_ARG, "yue_cnet_set_pairs: need 1 <= m, n < 2^31 - 1 and nnz >= 0");
-    int rc = check_csr(u_ptr, u_items, m, n, nnz, "user-major");
-    if (!rc) rc = check_csr(i_ptr, i_users, n, m, nnz, "item-major");
+    int rc = check_rows("yue_cnet_set_pairs: user-major", u_ptr, m, u_items, n, nnz, Order::ascending);
+    if (!rc) rc = check_rows("yue_cnet_set_pairs: item-major", i_ptr, n, i_users, m, nnz, Order::ascending);
+    // (the skip-self index relies on the transpose)
+    if (!rc) rc = check_transpose("yue_cnet_set_pairs", m, u_ptr, u_items, n, i_ptr, i_users, [](int64_t, int64_t) { return true; });
     if (rc) return rc;
-    {   // the item-major lists must be the transpose of the user-major ones (the skip-self index relies on it)
-        std::vector<int64_t> at(i_ptr, i_ptr + n);
-        for (int64_t u = 0; u < m; ++u)
-            for (int64_t e = u_ptr[u]; e < u_ptr[u + 1]; ++e) {
-                const int32_t i = u_items[e];
-                const int64_t q = at[(size_t)i]++;
-                if (q >= i_ptr[i + 1] || i_users[q] != (int32_t)u)
-                    return fail(YUE_ERR_ARG, "yue_cnet_set_pairs: the item-major pairs are not the transpose of the user-major pairs (item " + std::to_string(i) + ")");
-            }
-    }
     HIPCHK(hipSetDevice(c->device));
     yue_cnet *k = nullptr;
     if ((rc = yue_host::state(c, c->cnet, &k))) return rc;
@@ -147,12 +125,11 @@ int yue_cnet_set_walks(yue_ctx *c, int64_t m, int64_t nw, int L, const int32_t *
     if (!c) return fail(YUE_ERR_ARG, "yue_cnet_set_walks: null context");
     if (m < 1 || m >= INT32_MAX || nw < 1 || L < 2 || L > yue::kCnetMaxL || nw * L >= INT32_MAX || !walks)
         return fail(YUE_ERR_ARG, "yue_cnet_set_walks: need 1 <= m < 2^31 - 1, nw >= 1, 2 <= L <= 64, fewer than 2^31 entries");
-    for (int64_t e = 0; e < nw * L; ++e)
-        if (walks[e] < 0 || walks[e] >= m) return fail(YUE_ERR_ARG, "yue_cnet_set_walks: user id out of range");
+    int rc = check_ids("yue_cnet_set_walks: user", walks, nw * L, m);
+    if (rc) return rc;
     HIPCHK(hipSetDevice(c->device));
     yue_cnet *k = nullptr;
-    int rc = yue_host::state(c, c->cnet, &k);
-    if (rc) return rc;
+    if ((rc = yue_host::state(c, c->cnet, &k))) return rc;
     new_walks(k, m, 0, L);
     if ((rc = upload(k->walks, walks, nw * L))) return rc;
     new_walks(k, m, nw, L);
@@ -163,14 +140,11 @@ int yue_cnet_set_sentences(yue_ctx *c, int64_t m, int64_t ns, const int64_t *ptr
     if (!c) return fail(YUE_ERR_ARG, "yue_cnet_set_sentences: null context");
     if (m < 1 || m >= INT32_MAX || ns < 1 || !ptr || ptr[0] != 0 || ptr[ns] < 1 || ptr[ns] >= INT32_MAX || !ids)
         return fail(YUE_ERR_ARG, "yue_cnet_set_sentences: need 1 <= m < 2^31 - 1, ns >= 1, a pointer from 0 to the words, 1 <= words < 2^31 - 1");
-    for (int64_t q = 0; q < ns; ++q)
-        if (ptr[q + 1] < ptr[q]) return fail(YUE_ERR_ARG, "yue_cnet_set_sentences: the pointer must be non-decreasing");
-    for (int64_t e = 0; e < ptr[ns]; ++e)
-        if (ids[e] < 0 || ids[e] >= m) return fail(YUE_ERR_ARG, "yue_cnet_set_sentences: id out of range");
+    int rc = check_rows("yue_cnet_set_sentences: sentence", ptr, ns, ids, m, yue_host::kNoTotal, Order::any);
+    if (rc) return rc;
     HIPCHK(hipSetDevice(c->device));
     yue_cnet *k = nullptr;
-    int rc = yue_host::state(c, c->cnet, &k);
-    if (rc) return rc;
+    if ((rc = yue_host::state(c, c->cnet, &k))) return rc;
     new_walks(k, m, 0, 0);
     k->s_ptr.assign(ptr, ptr + ns + 1);
     k->s_ids.assign(ids, ids + ptr[ns]);

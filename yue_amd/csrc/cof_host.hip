@@ -162,16 +162,10 @@ int yue_cof_set_sppmi(yue_ctx *c, const int64_t *ptr, const int32_t *idx, const 
     if (!c || !c->have_factors) return fail(YUE_ERR_ARG, "yue_cof_set_sppmi: call yue_set_factors first (n)");
     if (nnz < 0 || !ptr || (nnz > 0 && (!idx || !val))) return fail(YUE_ERR_ARG, "yue_cof_set_sppmi: null array or negative nnz");
     const int64_t n = c->n;
-    if (ptr[0] != 0 || ptr[n] != nnz) return fail(YUE_ERR_ARG, "yue_cof_set_sppmi: the pointer must run from 0 to nnz");
-    for (int64_t i = 0; i < n; ++i) {
-        if (ptr[i + 1] < ptr[i]) return fail(YUE_ERR_ARG, "yue_cof_set_sppmi: the pointer must be non-decreasing");
-        for (int64_t e = ptr[i]; e < ptr[i + 1]; ++e) {
-            if (idx[e] < 0 || idx[e] >= n) return fail(YUE_ERR_ARG, "yue_cof_set_sppmi: context id out of range in row " + std::to_string(i));
-            if (e > ptr[i] && idx[e] <= idx[e - 1]) return fail(YUE_ERR_ARG, "yue_cof_set_sppmi: row " + std::to_string(i) + " is not ascending");
-            if (idx[e] == i) return fail(YUE_ERR_ARG, "yue_cof_set_sppmi: row " + std::to_string(i) + " holds a diagonal entry");
-            if (!std::isfinite(val[e])) return fail(YUE_ERR_ARG, "yue_cof_set_sppmi: row " + std::to_string(i) + " holds a value that is not finite");
-        }
-    }
+    int rc = check_rows("yue_cof_set_sppmi: SPPMI", ptr, n, idx, n, nnz, Order::ascending, yue_host::kNoLimit, [&](int64_t i, int64_t e) {
+        return idx[e] == i ? "holds a diagonal entry" : !std::isfinite(val[e]) ? "holds a value that is not finite" : nullptr;
+    });
+    if (rc) return rc;
     for (int64_t i = 0; i < n; ++i)                      // symmetric: (j, i) exists with the same value (rows ascending: binary search)
         for (int64_t e = ptr[i]; e < ptr[i + 1]; ++e) {
             const int32_t j = idx[e];
@@ -181,8 +175,7 @@ int yue_cof_set_sppmi(yue_ctx *c, const int64_t *ptr, const int32_t *idx, const 
                 return fail(YUE_ERR_ARG, "yue_cof_set_sppmi: not symmetric at (" + std::to_string(i) + ", " + std::to_string(j) + ")");
         }
     yue_cof *x = nullptr;
-    int rc = yue_host::state(c, c->cof, &x);
-    if (rc) return rc;
+    if ((rc = yue_host::state(c, c->cof, &x))) return rc;
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
     x->sp_n = -1;

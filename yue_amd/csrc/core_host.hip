@@ -99,15 +99,11 @@ int yue_set_interactions(yue_ctx *c, const int64_t *indptr, const int32_t *indic
     if (!c->have_factors) return fail(YUE_ERR_ARG, "yue_set_interactions: call yue_set_factors first (m, n)");
     HIPCHK(hipSetDevice(c->device));
     const int64_t m = c->m, n = c->n;
-    if (indptr[0] != 0 || ev_ptr[0] != 0) return fail(YUE_ERR_ARG, "yue_set_interactions: indptr[0] and ev_ptr[0] must be 0");
-    for (int64_t u = 0; u < m; ++u) {
-        if (indptr[u + 1] < indptr[u] || ev_ptr[u + 1] < ev_ptr[u]) return fail(YUE_ERR_ARG, "yue_set_interactions: offsets must be non-decreasing");
-        for (int64_t t = indptr[u]; t < indptr[u + 1]; ++t) {
-            if (indices[t] < 0 || indices[t] >= n) return fail(YUE_ERR_ARG, "yue_set_interactions: item id out of range");
-            if (t > indptr[u] && indices[t] <= indices[t - 1]) return fail(YUE_ERR_ARG, "yue_set_interactions: rows must be sorted and unique");
-        }
+    int rc = check_rows("yue_set_interactions: interaction", indptr, m, indices, n, yue_host::kNoTotal, Order::ascending);
+    if (!rc) rc = check_rows("yue_set_interactions: event", ev_ptr, m, ev_i, n, yue_host::kNoTotal, Order::any);
+    if (rc) return rc;
+    for (int64_t u = 0; u < m; ++u)
         if (indptr[u + 1] - indptr[u] >= n) return fail(YUE_ERR_ARG, "yue_set_interactions: a user listened to every item (the reference's sampler would never return, BPR.py:47)");
-    }
     const int64_t nnz = indptr[m], E = ev_ptr[m];
     {   // the update kernel addresses P relative to a batch's first user with 31-bit byte offsets
         int64_t prev = -1, max_gap = 0;
@@ -116,10 +112,7 @@ int yue_set_interactions(yue_ctx *c, const int64_t *indptr, const int32_t *indic
     }
     std::vector<int32_t> evu((size_t)E);
     for (int64_t u = 0; u < m; ++u)
-        for (int64_t e = ev_ptr[u]; e < ev_ptr[u + 1]; ++e) {
-            if (ev_i[e] < 0 || ev_i[e] >= n) return fail(YUE_ERR_ARG, "yue_set_interactions: event item out of range");
-            evu[(size_t)e] = (int32_t)u;
-        }
+        for (int64_t e = ev_ptr[u]; e < ev_ptr[u + 1]; ++e) evu[(size_t)e] = (int32_t)u;
     c->E = E; c->nnz = nnz;
     c->h_ev_ptr.assign(ev_ptr, ev_ptr + m + 1);
     c->all_users_have_events = true;

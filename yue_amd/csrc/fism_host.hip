@@ -36,18 +36,8 @@ int yue_fism_get_model(yue_ctx *c, double *P, float *Q, double *Bi) {
 }
 
 namespace {
-// checks a CSR of item rows (user_ptr[rows+1], items) against the uploaded model
-int fism_check_rows(yue_ctx *c, const int64_t *ptr, int64_t rows, const int32_t *items, const char *who) {
-    if (rows < 0 || !ptr || ptr[0] != 0) return fail(YUE_ERR_ARG, std::string(who) + ": bad row pointer");
-    for (int64_t r = 0; r < rows; ++r) if (ptr[r + 1] < ptr[r]) return fail(YUE_ERR_ARG, std::string(who) + ": row pointer must be non-decreasing");
-    const int64_t E = ptr[rows];
-    if (E > 0 && !items) return fail(YUE_ERR_ARG, std::string(who) + ": null items");
-    for (int64_t e = 0; e < E; ++e) if (items[e] < 0 || items[e] >= c->fn) return fail(YUE_ERR_ARG, std::string(who) + ": item id out of range");
-    return YUE_OK;
-}
-// ... and uploads it (checked: fism_check_rows has passed already)
-int fism_upload_rows(yue_ctx *c, const int64_t *ptr, int64_t rows, const int32_t *items, const char *who, bool checked = false) {
-    if (!checked) { const int rc = fism_check_rows(c, ptr, rows, items, who); if (rc) return rc; }
+// uploads a CSR of item rows (user_ptr[rows + 1], items) that check_rows has passed against the uploaded model
+int fism_upload_rows(yue_ctx *c, const int64_t *ptr, int64_t rows, const int32_t *items) {
     const int64_t E = ptr[rows];
     HIPCHK(c->f_ptr.resize((size_t)rows + 1)); HIPCHK(c->f_items.resize((size_t)std::max<int64_t>(E, 1)));
     HIPCHK(hipMemcpyAsync(c->f_ptr.p, ptr, ((size_t)rows + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
@@ -95,9 +85,9 @@ int yue_fism_epoch(yue_ctx *c, const int64_t *user_ptr, int64_t m, const int32_t
     if (!c || c->fn == 0) return fail(YUE_ERR_ARG, "yue_fism_epoch: no FISM model uploaded");
     if (m <= 0 || rho < 1 || !coef || (n_negs > 0 && !negs)) return fail(YUE_ERR_ARG, "yue_fism_epoch: bad argument");
     HIPCHK(hipSetDevice(c->device));
-    int rc = fism_check_rows(c, user_ptr, m, ev_i, "yue_fism_epoch");
+    int rc = check_rows("yue_fism_epoch: item", user_ptr, m, ev_i, c->fn, yue_host::kNoTotal, Order::any);
     if (rc || (rc = fism_check_draws(c, user_ptr, m, ev_i, negs, n_negs, rho, "yue_fism_epoch"))) return rc;
-    if ((rc = fism_upload_rows(c, user_ptr, m, ev_i, "yue_fism_epoch", true))) return rc;
+    if ((rc = fism_upload_rows(c, user_ptr, m, ev_i))) return rc;
     int64_t widest = 1;
     for (int64_t u = 0; u < m; ++u) widest = std::max(widest, user_ptr[u + 1] - user_ptr[u]);
     HIPCHK(c->f_negs.resize((size_t)std::max<int64_t>(n_negs, 1))); HIPCHK(c->f_coef.resize((size_t)m)); HIPCHK(c->f_x.resize((size_t)widest * c->fk));
@@ -125,9 +115,9 @@ int yue_fism_rounds(yue_ctx *c, const int64_t *user_ptr, int64_t m, const int32_
     if (!c || c->fn == 0) return fail(YUE_ERR_ARG, "yue_fism_rounds: no FISM model uploaded");
     if (m <= 0 || rho < 1 || round_users < 1 || !coef || (n_negs > 0 && !negs)) return fail(YUE_ERR_ARG, "yue_fism_rounds: bad argument");
     HIPCHK(hipSetDevice(c->device));
-    int rc = fism_check_rows(c, user_ptr, m, ev_i, "yue_fism_rounds");
+    int rc = check_rows("yue_fism_rounds: item", user_ptr, m, ev_i, c->fn, yue_host::kNoTotal, Order::any);
     if (rc || (rc = fism_check_draws(c, user_ptr, m, ev_i, negs, n_negs, rho, "yue_fism_rounds"))) return rc;
-    if ((rc = fism_upload_rows(c, user_ptr, m, ev_i, "yue_fism_rounds", true))) return rc;
+    if ((rc = fism_upload_rows(c, user_ptr, m, ev_i))) return rc;
     const int64_t E = user_ptr[m];
     // per user: first draw, the sorted unique list of the items it touches, and every event's / draw's position in it
     std::vector<int64_t> neg_ptr((size_t)m + 1, 0), uq_ptr((size_t)m + 1, 0);
@@ -292,8 +282,8 @@ int yue_fism_scores(yue_ctx *c, const int32_t *items, int64_t n_items, double *o
     if (!c || c->fn == 0 || !out_n) return fail(YUE_ERR_ARG, "yue_fism_scores: no FISM model uploaded");
     HIPCHK(hipSetDevice(c->device));
     const int64_t ptr[2] = {0, n_items};
-    int rc = fism_upload_rows(c, ptr, 1, items, "yue_fism_scores");
-    if (rc) return rc;
+    int rc = check_rows("yue_fism_scores: item", ptr, 1, items, c->fn, yue_host::kNoTotal, Order::any);
+    if (rc || (rc = fism_upload_rows(c, ptr, 1, items))) return rc;
     if ((rc = fism_score_rows(c, 1))) return rc;
     HIPCHK(hipMemcpyAsync(out_n, c->f_scores.p, (size_t)c->fn * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -307,8 +297,8 @@ int yue_fism_topn_scan(yue_ctx *c, const int64_t *row_ptr, const int32_t *row_it
     if (nu == 0) return YUE_OK;
     if (nu * c->fn >= (1ll << 31)) return fail(YUE_ERR_ARG, "yue_fism_topn_scan: users x items of one call must stay below 2^31 (call in chunks)");
     HIPCHK(hipSetDevice(c->device));
-    int rc = fism_upload_rows(c, row_ptr, nu, row_items, "yue_fism_topn_scan");
-    if (rc) return rc;
+    int rc = check_rows("yue_fism_topn_scan: item", row_ptr, nu, row_items, c->fn, yue_host::kNoTotal, Order::any);
+    if (rc || (rc = fism_upload_rows(c, row_ptr, nu, row_items))) return rc;
     if ((rc = fism_score_rows(c, nu))) return rc;
     HIPCHK(c->f_ids.resize((size_t)nu * N)); HIPCHK(c->f_out_sc.resize((size_t)nu * N)); HIPCHK(c->f_flags.resize((size_t)nu));
     hipLaunchKernelGGL(yue::k_fism_select, dim3((unsigned)((nu + 63) / 64)), dim3(64), 0, c->stream, c->f_scores.p, c->fn, nu, N,

@@ -14,12 +14,15 @@
 //   cdae_host.hip   CDAE (sparse encoder, sampled decoder, gradients regrouped by item, dense Adam on five variables)
 //   gcn_host.hpp    what those two share (header only): the graph on the device and its hub parts, a product's launches, the
 //                   minibatch, the phase timer
+//   input_checks.hpp  what a caller uploads as row lists, checked before a kernel indexes with it (header only, no HIP call):
+//                   check_rows (the whole pointer, then the ids), check_transpose, check_ids, and fail()'s declaration
 // Ownership: every device allocation is a DevBuf, every event an Event, every subsystem's state a StatePtr
 // member of the context made by state(); each frees itself with its owner, so yue_ctx_destroy ends in `delete c` and no unit
 // keeps a list of things to release.  The raw HIP calls for both stand in this header and nowhere else, as do upload / download
 // (blocking copies into and out of a DevBuf) and elapsed (the time between two events) -- tests/test_host_ownership.py.
 #pragma once
 #include "../../include/yue_hip.h"
+#include "input_checks.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -47,8 +50,6 @@ struct yue_cdae;                                     // cdae_host.hip: user CSR,
 struct yue_ipf;                                      // ipf_host.hip: session temporal graph, weights, per-slot work arrays of IPF
 
 namespace yue_host {
-
-int fail(int code, const std::string &msg);          // sets the thread-local message of yue_last_error(), returns code
 
 #define HIPCHK(expr)                                                                              \
     do {                                                                                          \
@@ -161,6 +162,10 @@ auto with_kr(int k, F &&f) {
 
 using yue_host::DevBuf;
 using yue_host::Event;
+using yue_host::Order;
+using yue_host::check_ids;
+using yue_host::check_rows;
+using yue_host::check_transpose;
 
 struct yue_ctx {
     int device = 0;

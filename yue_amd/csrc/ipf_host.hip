@@ -24,28 +24,6 @@ struct yue_ipf {
 
 namespace {
 
-// ptr[rows+1] from 0, non-decreasing; ids in [0, bound); rows no longer than max_row; distinct within a row when asked
-int check_lists(const int64_t *ptr, const int32_t *ids, int64_t rows, int64_t bound, int64_t max_row, bool distinct,
-                std::vector<int64_t> &mark, const char *what) {
-    const std::string at = std::string("yue_ipf_set_graph: ") + what;
-    if (!ptr) return fail(YUE_ERR_ARG, at + ": null pointer array");
-    if (ptr[0] != 0) return fail(YUE_ERR_ARG, at + " pointer must start at 0");
-    for (int64_t r = 0; r < rows; ++r) {
-        if (ptr[r + 1] < ptr[r]) return fail(YUE_ERR_ARG, at + " pointer must be non-decreasing");
-        if (ptr[r + 1] - ptr[r] > max_row) return fail(YUE_ERR_ARG, at + " row " + std::to_string(r) + " is too long (limit " + std::to_string(max_row) + ")");
-    }
-    if (ptr[rows] > 0 && !ids) return fail(YUE_ERR_ARG, at + ": null id array");
-    for (int64_t r = 0; r < rows; ++r)
-        for (int64_t e = ptr[r]; e < ptr[r + 1]; ++e) {
-            if (ids[e] < 0 || ids[e] >= bound) return fail(YUE_ERR_ARG, at + " id out of range");
-            if (distinct) {
-                if (mark[(size_t)ids[e]] == r) return fail(YUE_ERR_ARG, at + " rows must hold distinct ids");
-                mark[(size_t)ids[e]] = r;
-            }
-        }
-    return YUE_OK;
-}
-
 // work arrays for `slots` workgroups, cleared when new or after a failed launch
 int ensure_slots(yue_ctx *c, yue_ipf *g, int64_t slots) {
     const size_t sm = (size_t)slots * (size_t)g->m, sn = (size_t)slots * (size_t)g->n;
@@ -117,11 +95,10 @@ int yue_ipf_set_graph(yue_ctx *c, int64_t m, int64_t n, const int64_t *u_ptr, co
         return fail(YUE_ERR_ARG, "yue_ipf_set_graph: need 1 <= m, n < 2^26");
     if (!w_user || !w_sess || !p_i2u || !p_i2s) return fail(YUE_ERR_ARG, "yue_ipf_set_graph: null weight array");
     const int64_t max_list = ((int64_t)1 << yue::kIpfKBits) - 1, max_holders = ((int64_t)1 << yue::kIpfPosBits) - 1;
-    std::vector<int64_t> mark((size_t)std::max(m, n), -1);
-    int rc = check_lists(u_ptr, u_items, m, n, max_list, true, mark, "user lists");
-    if (!rc) { std::fill(mark.begin(), mark.end(), -1); rc = check_lists(s_ptr, s_items, m, n, max_list, true, mark, "session lists"); }
-    if (!rc) { std::fill(mark.begin(), mark.end(), -1); rc = check_lists(hu_ptr, hu_users, n, m, max_holders, true, mark, "item2user lists"); }
-    if (!rc) { std::fill(mark.begin(), mark.end(), -1); rc = check_lists(hs_ptr, hs_users, n, m, max_holders, true, mark, "item2session lists"); }
+    int rc = check_rows("yue_ipf_set_graph: user lists", u_ptr, m, u_items, n, yue_host::kNoTotal, Order::distinct, max_list);
+    if (!rc) rc = check_rows("yue_ipf_set_graph: session lists", s_ptr, m, s_items, n, yue_host::kNoTotal, Order::distinct, max_list);
+    if (!rc) rc = check_rows("yue_ipf_set_graph: item2user lists", hu_ptr, n, hu_users, m, yue_host::kNoTotal, Order::distinct, max_holders);
+    if (!rc) rc = check_rows("yue_ipf_set_graph: item2session lists", hs_ptr, n, hs_users, m, yue_host::kNoTotal, Order::distinct, max_holders);
     if (rc) return rc;
     if (hs_ptr[n] > 0 && !hs_pos) return fail(YUE_ERR_ARG, "yue_ipf_set_graph: null item2session positions");
     for (int64_t e = 0; e < hs_ptr[n]; ++e)
@@ -156,8 +133,7 @@ int yue_ipf_topn(yue_ctx *c, const int32_t *users, int64_t nu, int N, int32_t *i
     if (N < 1 || N > yue::kIpfMaxN) return fail(YUE_ERR_ARG, "yue_ipf_topn: N = " + std::to_string(N) + " is not supported (1 <= N <= 100)");
     if (nu < 0 || nu >= INT32_MAX || (nu > 0 && (!users || !ids_out || !scores_out || !len_out)))
         return fail(YUE_ERR_ARG, "yue_ipf_topn: need 0 <= nu < 2^31 - 1 and non-null arrays");
-    for (int64_t b = 0; b < nu; ++b)
-        if (users[b] < 0 || users[b] >= g->m) return fail(YUE_ERR_ARG, "yue_ipf_topn: user id out of range");
+    if ((rc = check_ids("yue_ipf_topn: user", users, nu, g->m))) return rc;
     if (nu == 0) return YUE_OK;
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(g->users.resize((size_t)nu)); HIPCHK(g->ids_out.resize((size_t)nu * N)); HIPCHK(g->scores_out.resize((size_t)nu * N));

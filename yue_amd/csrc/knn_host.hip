@@ -26,22 +26,6 @@ struct yue_knn {
 
 namespace {
 
-// one direction's CSR: ptr[rows+1] from 0 to nnz, ids sorted-unique in [0, ids_bound), counts (when given) >= 1
-int check_csr(const int64_t *ptr, const int32_t *ids, const int32_t *cnt, int64_t rows, int64_t ids_bound, int64_t nnz, const char *what) {
-    const std::string at = std::string("yue_knn_set_pairs: ") + what;
-    if (!ptr || (nnz > 0 && !ids)) return fail(YUE_ERR_ARG, at + ": null array");
-    if (ptr[0] != 0 || ptr[rows] != nnz) return fail(YUE_ERR_ARG, at + " pointer must run from 0 to nnz");
-    for (int64_t r = 0; r < rows; ++r) {
-        if (ptr[r + 1] < ptr[r]) return fail(YUE_ERR_ARG, at + " pointer must be non-decreasing");
-        for (int64_t e = ptr[r]; e < ptr[r + 1]; ++e) {
-            if (ids[e] < 0 || ids[e] >= ids_bound) return fail(YUE_ERR_ARG, at + " id out of range");
-            if (e > ptr[r] && ids[e] <= ids[e - 1]) return fail(YUE_ERR_ARG, at + " rows must be sorted and unique");
-            if (cnt && cnt[e] < 1) return fail(YUE_ERR_ARG, at + " counts must be >= 1");
-        }
-    }
-    return YUE_OK;
-}
-
 yue::KnnArgs base_args(const yue_ctx *c, const yue_knn *k) {
     yue::KnnArgs a{};
     a.m = k->m; a.n = k->n;
@@ -71,19 +55,12 @@ int yue_knn_set_pairs(yue_ctx *c, int64_t m, int64_t n, const int64_t *u_ptr, co
     if (m >= INT32_MAX || n >= ((int64_t)1 << 26))
         return fail(YUE_ERR_ARG, "yue_knn_set_pairs: m must be below 2^31 - 1 and n below 2^26 (similarities are compared as exact integer ratios)");
     if (nnz > 0 && !u_counts) return fail(YUE_ERR_ARG, "yue_knn_set_pairs: null user-major counts");
-    int rc = check_csr(u_ptr, u_items, u_counts, m, n, nnz, "user-major");
-    if (!rc) rc = check_csr(i_ptr, i_users, nullptr, n, m, nnz, "item-major");
+    int rc = check_rows("yue_knn_set_pairs: user-major", u_ptr, m, u_items, n, nnz, Order::ascending, yue_host::kNoLimit,
+                        [&](int64_t, int64_t e) { return u_counts[e] < 1 ? "counts must be >= 1" : nullptr; });
+    if (!rc) rc = check_rows("yue_knn_set_pairs: item-major", i_ptr, n, i_users, m, nnz, Order::ascending);
+    // (users ascending within an item: the cursors rely on it)
+    if (!rc) rc = check_transpose("yue_knn_set_pairs", m, u_ptr, u_items, n, i_ptr, i_users, [](int64_t, int64_t) { return true; });
     if (rc) return rc;
-    {   // the item-major lists must be the transpose of the user-major ones (users ascending: the cursors rely on it)
-        std::vector<int64_t> at(i_ptr, i_ptr + n);
-        for (int64_t u = 0; u < m; ++u)
-            for (int64_t e = u_ptr[u]; e < u_ptr[u + 1]; ++e) {
-                const int32_t i = u_items[e];
-                const int64_t q = at[(size_t)i]++;
-                if (q >= i_ptr[i + 1] || i_users[q] != (int32_t)u)
-                    return fail(YUE_ERR_ARG, "yue_knn_set_pairs: the item-major pairs are not the transpose of the user-major pairs (item " + std::to_string(i) + ")");
-            }
-    }
     HIPCHK(hipSetDevice(c->device));
     yue_knn *k = nullptr;
     if ((rc = yue_host::state(c, c->knn, &k))) return rc;
@@ -127,8 +104,7 @@ int yue_knn_topn(yue_ctx *c, const int32_t *users, int64_t nu, int N, int32_t *i
     if (N < 1 || N > yue::kKnnMaxN) return fail(YUE_ERR_ARG, "yue_knn_topn: N = " + std::to_string(N) + " is not supported (1 <= N <= 100)");
     if (nu < 0 || nu >= INT32_MAX || (nu > 0 && (!users || !ids_out || !scores_out || !len_out)))
         return fail(YUE_ERR_ARG, "yue_knn_topn: need 0 <= nu < 2^31 - 1 and non-null arrays");
-    for (int64_t b = 0; b < nu; ++b)
-        if (users[b] < 0 || users[b] >= k->m) return fail(YUE_ERR_ARG, "yue_knn_topn: user id out of range");
+    if ((rc = check_ids("yue_knn_topn: user", users, nu, k->m))) return rc;
     if (nu == 0) return YUE_OK;
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(k->users.resize((size_t)nu)); HIPCHK(k->ids.resize((size_t)nu * N)); HIPCHK(k->scores.resize((size_t)nu * N)); HIPCHK(k->len.resize((size_t)nu));

@@ -24,21 +24,6 @@ namespace {
 
 enum { kForward = 0, kBatch = 1, kBackward = 2, kAdam = 3, kPhases = 4 };
 
-// one side's lists: ptr[0] = 0, ascending ptr, ids strictly ascending within a row and below `other`, finite weights
-int check_side(const char *side, int64_t rows, int64_t other, const int64_t *ptr, const int32_t *ids, const float *w) {
-    const std::string who = std::string("yue_lgcn_set_graph: ") + side;
-    if (ptr[0] != 0) return fail(YUE_ERR_ARG, who + " ptr[0] must be 0");
-    for (int64_t r = 0; r < rows; ++r) {
-        if (ptr[r + 1] < ptr[r]) return fail(YUE_ERR_ARG, who + " ptr must ascend (row " + std::to_string(r) + ")");
-        for (int64_t p = ptr[r]; p < ptr[r + 1]; ++p) {
-            if (ids[p] < 0 || ids[p] >= other) return fail(YUE_ERR_ARG, who + " row " + std::to_string(r) + ": id out of range");
-            if (p > ptr[r] && ids[p] <= ids[p - 1]) return fail(YUE_ERR_ARG, who + " row " + std::to_string(r) + ": ids must be sorted and unique");
-            if (!std::isfinite(w[p])) return fail(YUE_ERR_ARG, who + " row " + std::to_string(r) + ": weight not finite");
-        }
-    }
-    return YUE_OK;
-}
-
 int lgcn_ready(yue_ctx *c, yue_lgcn **out, int layers, const char *who) {
     if (!c) return fail(YUE_ERR_ARG, std::string(who) + ": null context");
     if (!c->have_factors) return fail(YUE_ERR_ARG, std::string(who) + ": call yue_set_factors first (U, V)");
@@ -116,23 +101,16 @@ int yue_lgcn_set_graph(yue_ctx *c, int64_t m, int64_t n, const int64_t *u_ptr, c
                        const int32_t *i_users, const float *i_w) {
     if (!c || !u_ptr || !i_ptr) return fail(YUE_ERR_ARG, "yue_lgcn_set_graph: null argument");
     if (m <= 0 || n <= 0 || m + n >= (1ll << 31)) return fail(YUE_ERR_ARG, "yue_lgcn_set_graph: need m, n > 0 and m + n < 2^31");
-    const int64_t half = u_ptr[0] == 0 ? u_ptr[m] : -1;
+    const int64_t half = u_ptr[m];
     if (half > 0 && (!u_items || !u_w || !i_users || !i_w)) return fail(YUE_ERR_ARG, "yue_lgcn_set_graph: null argument");
-    int rc;
-    if ((rc = check_side("user", m, n, u_ptr, u_items, u_w)) || (rc = check_side("item", n, m, i_ptr, i_users, i_w))) return rc;
+    const auto finite = [](const float *w) { return [w](int64_t, int64_t p) { return std::isfinite(w[p]) ? nullptr : "weight not finite"; }; };
+    int rc = check_rows("yue_lgcn_set_graph: user-side", u_ptr, m, u_items, n, yue_host::kNoTotal, Order::ascending, yue_host::kNoLimit, finite(u_w));
+    if (rc) return rc;
     // symmetry: the user lists transposed (users ascend within an item, as the item lists must) equal the item lists
     if (i_ptr[n] != half) return fail(YUE_ERR_ARG, "yue_lgcn_set_graph: the graph is not symmetric (the two sides hold different numbers of pairs)");
-    std::vector<int64_t> at((size_t)n + 1, 0);
-    for (int64_t p = 0; p < half; ++p) at[(size_t)u_items[p] + 1]++;
-    for (int64_t r = 0; r < n; ++r) at[(size_t)r + 1] += at[(size_t)r];
-    for (int64_t r = 0; r <= n; ++r)
-        if (at[(size_t)r] != i_ptr[r]) return fail(YUE_ERR_ARG, "yue_lgcn_set_graph: the graph is not symmetric (item " + std::to_string(std::max<int64_t>(r - 1, 0)) + ")");
-    for (int64_t u = 0; u < m; ++u)
-        for (int64_t p = u_ptr[u]; p < u_ptr[u + 1]; ++p) {
-            const int64_t q = at[(size_t)u_items[p]]++;
-            if (i_users[q] != u || i_w[q] != u_w[p])
-                return fail(YUE_ERR_ARG, "yue_lgcn_set_graph: the graph is not symmetric (user " + std::to_string(u) + ", item " + std::to_string(u_items[p]) + ")");
-        }
+    if ((rc = check_rows("yue_lgcn_set_graph: item-side", i_ptr, n, i_users, m, yue_host::kNoTotal, Order::ascending, yue_host::kNoLimit, finite(i_w))) ||
+        (rc = check_transpose("yue_lgcn_set_graph: the graph is not symmetric", m, u_ptr, u_items, n, i_ptr, i_users, [&](int64_t p, int64_t q) { return i_w[q] == u_w[p]; })))
+        return rc;
     yue_lgcn *s = nullptr;
     if ((rc = yue_host::state(c, c->lgcn, &s))) return rc;
     HIPCHK(hipSetDevice(c->device));

@@ -181,19 +181,12 @@ int yue_ngcf_set_graph(yue_ctx *c, int64_t m, int64_t n, const int64_t *ptr, con
     if (!c || !ptr) return fail(YUE_ERR_ARG, "yue_ngcf_set_graph: null argument");
     if (m <= 0 || n <= 0 || m + n >= (1ll << 31)) return fail(YUE_ERR_ARG, "yue_ngcf_set_graph: need m, n > 0 and m + n < 2^31");
     const int64_t N = m + n;
-    if (ptr[0] != 0) return fail(YUE_ERR_ARG, "yue_ngcf_set_graph: ptr[0] must be 0");
-    for (int64_t r = 0; r < N; ++r)
-        if (ptr[r + 1] < ptr[r]) return fail(YUE_ERR_ARG, "yue_ngcf_set_graph: ptr must ascend (row " + std::to_string(r) + ")");
     const int64_t nnz = ptr[N];
     if (nnz >= (1ll << 31)) return fail(YUE_ERR_ARG, "yue_ngcf_set_graph: needs fewer than 2^31 entries");
     if (nnz > 0 && (!col || !w)) return fail(YUE_ERR_ARG, "yue_ngcf_set_graph: null argument");
-    for (int64_t r = 0; r < N; ++r)
-        for (int64_t p = ptr[r]; p < ptr[r + 1]; ++p) {
-            if (col[p] < 0 || col[p] >= N) return fail(YUE_ERR_ARG, "yue_ngcf_set_graph: row " + std::to_string(r) + ": column out of range");
-            if (p > ptr[r] && col[p] <= col[p - 1]) return fail(YUE_ERR_ARG, "yue_ngcf_set_graph: row " + std::to_string(r) + ": columns must be sorted and unique");
-            if (!std::isfinite(w[p])) return fail(YUE_ERR_ARG, "yue_ngcf_set_graph: row " + std::to_string(r) + ": weight not finite");
-        }
-    int rc;
+    int rc = check_rows("yue_ngcf_set_graph: graph", ptr, N, col, N, yue_host::kNoTotal, Order::ascending, yue_host::kNoLimit,
+                        [&](int64_t, int64_t p) { return std::isfinite(w[p]) ? nullptr : "weight not finite"; });
+    if (rc) return rc;
     yue_ngcf *s = nullptr;
     if ((rc = yue_host::state(c, c->ngcf, &s))) return rc;
     HIPCHK(hipSetDevice(c->device));

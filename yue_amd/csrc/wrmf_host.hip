@@ -31,21 +31,6 @@ struct yue_wrmf {
 
 namespace {
 
-// checks one direction's CSR: ptr[rows+1] from 0 to nnz, ids sorted-unique in [0, ids_bound), counts >= 1
-int check_csr(const int64_t *ptr, const int32_t *ids, const int32_t *cnt, int64_t rows, int64_t ids_bound, int64_t nnz, const char *what) {
-    if (!ptr || (nnz > 0 && (!ids || !cnt))) return fail(YUE_ERR_ARG, std::string("yue_wrmf_set_pairs: null ") + what + " array");
-    if (ptr[0] != 0 || ptr[rows] != nnz) return fail(YUE_ERR_ARG, std::string("yue_wrmf_set_pairs: ") + what + " pointer must run from 0 to nnz");
-    for (int64_t r = 0; r < rows; ++r) {
-        if (ptr[r + 1] < ptr[r]) return fail(YUE_ERR_ARG, std::string("yue_wrmf_set_pairs: ") + what + " pointer must be non-decreasing");
-        for (int64_t e = ptr[r]; e < ptr[r + 1]; ++e) {
-            if (ids[e] < 0 || ids[e] >= ids_bound) return fail(YUE_ERR_ARG, std::string("yue_wrmf_set_pairs: ") + what + " id out of range");
-            if (e > ptr[r] && ids[e] <= ids[e - 1]) return fail(YUE_ERR_ARG, std::string("yue_wrmf_set_pairs: ") + what + " rows must be sorted and unique");
-            if (cnt[e] < 1) return fail(YUE_ERR_ARG, std::string("yue_wrmf_set_pairs: ") + what + " counts must be >= 1");
-        }
-    }
-    return YUE_OK;
-}
-
 int upload_side(int64_t long_pairs, yue_wrmf_side &s, const int64_t *ptr, const int32_t *ids, const int32_t *cnt, int64_t rows, int64_t nnz) {
     s.rows = rows;
     // longest first (stable: equal lengths keep row order), then the long rows' chunks
@@ -128,19 +113,12 @@ int yue_wrmf_set_pairs(yue_ctx *c, const int64_t *u_ptr, const int32_t *u_items,
     if (!c || !c->have_factors) return fail(YUE_ERR_ARG, "yue_wrmf_set_pairs: call yue_set_factors first (m, n)");
     if (nnz < 0) return fail(YUE_ERR_ARG, "yue_wrmf_set_pairs: nnz must be >= 0");
     const int64_t m = c->m, n = c->n;
-    int rc = check_csr(u_ptr, u_items, u_counts, m, n, nnz, "user-major");
-    if (!rc) rc = check_csr(i_ptr, i_users, i_counts, n, m, nnz, "item-major");
+    if (nnz > 0 && (!u_counts || !i_counts)) return fail(YUE_ERR_ARG, "yue_wrmf_set_pairs: null counts array");
+    const auto counted = [](const int32_t *cnt) { return [cnt](int64_t, int64_t e) { return cnt[e] < 1 ? "counts must be >= 1" : nullptr; }; };
+    int rc = check_rows("yue_wrmf_set_pairs: user-major", u_ptr, m, u_items, n, nnz, Order::ascending, yue_host::kNoLimit, counted(u_counts));
+    if (!rc) rc = check_rows("yue_wrmf_set_pairs: item-major", i_ptr, n, i_users, m, nnz, Order::ascending, yue_host::kNoLimit, counted(i_counts));
+    if (!rc) rc = check_transpose("yue_wrmf_set_pairs", m, u_ptr, u_items, n, i_ptr, i_users, [&](int64_t e, int64_t q) { return i_counts[q] == u_counts[e]; });
     if (rc) return rc;
-    {   // the item-major view must be the transpose of the user-major one: walking users in order fills every item row in order
-        std::vector<int64_t> at(i_ptr, i_ptr + n);
-        for (int64_t u = 0; u < m; ++u)
-            for (int64_t e = u_ptr[u]; e < u_ptr[u + 1]; ++e) {
-                const int32_t i = u_items[e];
-                const int64_t q = at[(size_t)i]++;
-                if (q >= i_ptr[i + 1] || i_users[q] != (int32_t)u || i_counts[q] != u_counts[e])
-                    return fail(YUE_ERR_ARG, "yue_wrmf_set_pairs: the item-major pairs are not the transpose of the user-major pairs (item " + std::to_string(i) + ")");
-            }
-    }
     HIPCHK(hipSetDevice(c->device));
     yue_wrmf *w = nullptr;
     if ((rc = yue_host::state(c, c->wrmf, &w))) return rc;
