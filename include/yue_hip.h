@@ -600,6 +600,9 @@ int yue_cdae_step(yue_ctx *ctx, const int32_t *users, int64_t B, const int64_t *
 int yue_cdae_load_factors(yue_ctx *ctx);
 int yue_cdae_times(yue_ctx *ctx, int64_t *ns_out);
 
+/* APR (reference recommender/advanced/APR.py): declared in a header of its own, which sees the types above. */
+#include "yue_apr.h"
+
 /* Multi-GPU (one process per GPU, RCCL over xGMI).  Rank 0 creates the id, the caller ships
  * the 128 bytes to the other ranks (any side channel), every rank calls yue_comm_init. */
 int yue_comm_unique_id(void *id128_out);

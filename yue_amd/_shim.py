@@ -1,4 +1,4 @@
-"""ctypes binding of libyue_hip.so (include/yue_hip.h).
+"""ctypes binding of libyue_hip.so (include/yue_hip.h, and include/yue_apr.h, which it includes).
 
 This is the only route from the Python plugin surface to the numeric hot path: there is no
 CPU fallback.  If the library is missing or no MI355X is visible, calls fail loudly in the
@@ -6,7 +6,7 @@ reference's style -- print the message, exit(-1) (tool/config.py:9-11,
 base/IterativeRecommender.py:64-66) -- or raise YueHipError when ``raise_errors`` is set
 (tests use that).
 
-Every exported function's C signature stands once, in SIGNATURES; load_library() turns it into
+Every exported function's C signature stands once, in SIGNATURES (APR's in APR_SIGNATURES, beside its own header); load_library() turns it into
 ``restype`` and ``argtypes``, so a call site passes Python numbers and NumPy arrays as they are and
 ctypes converts or refuses each argument (tests/test_shim_signatures.py holds the table against the header).
 """
@@ -141,6 +141,18 @@ SIGNATURES = {
 }
 SYMBOLS = list(SIGNATURES)                                   # (checked against the header by tests/test_abi.py)
 
+# ... and every function include/yue_apr.h declares, which yue_hip.h includes (tests/test_apr_signatures.py)
+APR_SIGNATURES = {
+    'yue_apr_reset': 'ctx',
+    'yue_apr_pre_step': 'ctx i32* i32* i32* i64 f64 f64 i64 f64*',
+    'yue_apr_adv_step': 'ctx i32* i32* i32* i64 f64 f64 f64 i64 f64*',
+    'yue_apr_set_delta': 'ctx i32* i64 f32* i32* i64 f32*',
+    'yue_apr_get_delta': 'ctx f32* f32*',
+    'yue_apr_delta_update': 'ctx i32* i32* i32* i64 f64 f64 f32* f32*',
+    'yue_apr_grad': 'ctx int i32* i32* i32* i64 f64 f64* f32* f32*',
+    'yue_apr_times': 'ctx i64*',
+}
+
 
 class YueHipError(RuntimeError):
     def __init__(self, code, msg):
@@ -158,7 +170,7 @@ def load_library():
         if not os.path.exists(LIB_PATH):
             raise YueHipError(ERR_HIP, 'HIP library not built: %s (run `make -C yue_amd/csrc` or __graft_entry__.build())' % LIB_PATH)
         lib = C.CDLL(LIB_PATH)
-        for name, signature in SIGNATURES.items():
+        for name, signature in list(SIGNATURES.items()) + list(APR_SIGNATURES.items()):
             params, _, returns = signature.partition('->')
             fn = getattr(lib, name)
             fn.restype = TYPES[returns.strip() or 'int']
@@ -793,6 +805,58 @@ class Device(object):
         """Device ns of the last call's (encode, decode, regroup, adam) phases."""
         ns = (C.c_int64 * 4)()
         self._call('yue_cdae_times', ns)
+        return tuple(ns)
+
+    # -- APR (U = P, V = Q of set_factors, the moments of adam_reset; DESIGN.md section 23) -----
+    def apr_reset(self):
+        """Clears the adversarial perturbation."""
+        self._call('yue_apr_reset')
+
+    def apr_pre_step(self, u, i, j, lr, reg, step):
+        """One phase-1 step (softplus loss, the user rows regularised twice, the negative rows not), Adam.  Returns total_loss."""
+        u, i, j = _triplets(u, i, j, 'apr_pre_step')
+        return self._read('yue_apr_pre_step', 1, u, i, j, len(u), lr, reg, step)[0]
+
+    def apr_adv_step(self, u, i, j, lr, eps, regA, step):
+        """One phase-2 step: the perturbation from the batch's normalised gradient, then Adam on loss_adv.  Returns loss_adv."""
+        u, i, j = _triplets(u, i, j, 'apr_adv_step')
+        return self._read('yue_apr_adv_step', 1, u, i, j, len(u), lr, eps, regA, step)[0]
+
+    def apr_set_delta(self, users, rows_u, items, rows_v):
+        """The perturbation's rows: ascending distinct ids with one row [k] each; every other row is 0."""
+        users, items = _in(users, np.int32, True), _in(items, np.int32, True)
+        rows_u, rows_v = _in(rows_u, np.float32).reshape(-1, self.k), _in(rows_v, np.float32).reshape(-1, self.k)
+        nu, ni = len(rows_u), len(rows_v)
+        assert nu <= len(users) and ni <= len(items), 'apr_set_delta: one id per row'
+        self._call('yue_apr_set_delta', users, nu, rows_u if nu else None, items, ni, rows_v if ni else None)
+
+    def apr_get_delta(self):
+        """(dU [m, k], dV [n, k]): the perturbation, dense."""
+        dU, dV = np.empty((self.m, self.k), np.float32), np.empty((self.n, self.k), np.float32)
+        self._call('yue_apr_get_delta', dU, dV)
+        return dU, dV
+
+    def apr_delta_update(self, u, i, j, eps, regA):
+        """The first half of a phase-2 step: returns the raw gradients (gU [m, k], gV [n, k]) with respect to the standing
+        perturbation and installs the new one."""
+        u, i, j = _triplets(u, i, j, 'apr_delta_update')
+        gU, gV = np.empty((self.m, self.k), np.float32), np.empty((self.n, self.k), np.float32)
+        self._call('yue_apr_delta_update', u, i, j, len(u), eps, regA, gU, gV)
+        return gU, gV
+
+    def apr_grad(self, adversarial, u, i, j, reg):
+        """(loss, dLoss / dU, dLoss / dV) of the phase-1 loss (reg) or of loss_adv at the standing perturbation (reg = regA);
+        nothing moves."""
+        u, i, j = _triplets(u, i, j, 'apr_grad')
+        loss = C.c_double()
+        gU, gV = np.empty((self.m, self.k), np.float32), np.empty((self.n, self.k), np.float32)
+        self._call('yue_apr_grad', 1 if adversarial else 0, u, i, j, len(u), reg, C.byref(loss), gU, gV)
+        return loss.value, gU, gV
+
+    def apr_times(self):
+        """Device ns of the last call's (coefficient, parameter-row, perturbation-row, adam) phases."""
+        ns = (C.c_int64 * 4)()
+        self._call('yue_apr_times', ns)
         return tuple(ns)
 
     # -- multi-GPU ----------------------------------------------------------------------

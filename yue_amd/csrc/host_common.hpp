@@ -12,6 +12,7 @@
 //   lgcn_host.hip   LightGCN (graph propagation forward and backward, minibatch, Adam step)
 //   ngcf_host.hip   NGCF (weighted graph convolution: gather, MFMA layers forward and backward, weight gradients, Adam step)
 //   cdae_host.hip   CDAE (sparse encoder, sampled decoder, gradients regrouped by item, dense Adam on five variables)
+//   apr_host.hip    APR (pairwise minibatch gradient in fixed order, compact adversarial perturbation, Adam step)
 //   gcn_host.hpp    what those two share (header only): the graph on the device and its hub parts, a product's launches, the
 //                   minibatch, the phase timer
 //   input_checks.hpp  what a caller uploads as row lists, checked before a kernel indexes with it (header only, no HIP call):
@@ -47,6 +48,7 @@ struct yue_s2v;                                      // s2v_host.hip: biases, st
 struct yue_lgcn;                                     // lgcn_host.hip: the graph (gcn_host.hpp), layers and gradients of LightGCN
 struct yue_ngcf;                                     // ngcf_host.hip: the graph and its transpose (gcn_host.hpp), weights, layers and gradients of NGCF
 struct yue_cdae;                                     // cdae_host.hip: user CSR, the five variables with their moments, the batch's index arrays of CDAE
+struct yue_apr;                                      // apr_host.hip: the compact perturbation and the batch's index arrays of APR
 struct yue_ipf;                                      // ipf_host.hip: session temporal graph, weights, per-slot work arrays of IPF
 
 namespace yue_host {
@@ -334,6 +336,9 @@ struct yue_ctx {
     int64_t cdae_hubs = 0, cdae_parts = 0;   // ... such rows / segments and their parts in the last call (read-only options cdae_last_hubs / cdae_last_parts)
     int64_t cdae_saturated = 0;          // sampled outputs with y_pred == 1.0f in the last call (read-only option cdae_last_saturated)
     int64_t cdae_ns[4] = {0, 0, 0, 0};   // device time of the last call's encode, decode, regroup and adam phases (yue_cdae_times)
+    yue_host::StatePtr<yue_apr> apr{nullptr, nullptr};   // APR state (yue_apr_*), owned by apr_host.hip
+    int64_t apr_longest = 0;             // longest (triplet, role) list of a row in the last batch (read-only option apr_last_longest_row)
+    int64_t apr_ns[4] = {0, 0, 0, 0};    // device time of the last call's coefficient, row, normalise and adam phases (yue_apr_times)
 };
 
 namespace yue_host {

@@ -144,6 +144,8 @@ const Option kOptions[] = {
     {"cdae_last_hubs", YUE_AT(cdae_hubs)},
     {"cdae_last_parts", YUE_AT(cdae_parts)},
     {"cdae_last_saturated", YUE_AT(cdae_saturated)},
+    // APR (apr_host.hip)
+    {"apr_last_longest_row", YUE_AT(apr_longest)},
     // WRMF (wrmf_host.hip)
     {"wrmf_long_pairs", YUE_AT(opt_wrmf_long_pairs), set_ranged, yue_host::kWrmfStageHost, kNoEnd, "must be >= 32"},   // takes effect at the next yue_wrmf_set_pairs
     {"wrmf_last_ns", YUE_AT(wrmf_ns[0])},

@@ -4,7 +4,7 @@ import time
 from .tool.config import Config
 from .yue import Yue
 
-MENU = {'1': 'BPR', '2': 'FISM', '3': 'WRMF', '4': 'IPF', '5': 'UserKNN', 'a1': 'CUNE', 'a2': 'Song2vec', 'a4': 'CDAE', 'a6': 'ExpoMF', 'a7': 'CoFactor', 'a8': 'LightGCN', 'a9': 'NGCF'}
+MENU = {'1': 'BPR', '2': 'FISM', '3': 'WRMF', '4': 'IPF', '5': 'UserKNN', 'a1': 'CUNE', 'a2': 'Song2vec', 'a4': 'CDAE', 'a6': 'ExpoMF', 'a7': 'CoFactor', 'a8': 'LightGCN', 'a9': 'NGCF', 'a10': 'APR'}
 
 
 def main():
@@ -16,7 +16,7 @@ def main():
     print('Advanced Recommenders:')
     print('a1. CUNE (friends from -net hip or -friends, see recommender/advanced/CUNE.py)')
     print('a2. Song2vec (embedding from -emb hip or -emb FILE.npy, see recommender/advanced/Song2vec.py)')
-    print('a4. CDAE   a6. ExpoMF   a7. CoFactor   a8. LightGCN   a9. NGCF')
+    print('a4. CDAE   a6. ExpoMF   a7. CoFactor   a8. LightGCN   a9. NGCF   a10. APR')
     print('=' * 80)
     order = input('Please enter the num of the algorithm to run it:')
     start = time.time()

@@ -2,7 +2,7 @@
 
 Differences from the reference, all outside the numeric path: the class is imported with
 importlib instead of exec/eval, `mkl` is not needed, and only recommenders that exist in
-yue_amd.recommender are importable (BPR, FISM, WRMF, IPF, UserKNN, ExpoMF, CoFactor, CUNE, Song2vec, CDAE, LightGCN and NGCF in this build).
+yue_amd.recommender are importable (BPR, FISM, WRMF, IPF, UserKNN, ExpoMF, CoFactor, CUNE, Song2vec, CDAE, LightGCN, NGCF and APR in this build).
 
 One addition: ``record.setup=-format csr`` makes ``record`` a binary integer data set
 (yue_amd/data/arrays.py: save_csr / load_csr) that carries its own held-out items; it goes to the
