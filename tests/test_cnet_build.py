@@ -6,6 +6,8 @@ import re
 import shutil
 import subprocess
 
+from helpers.resource_usage import has_device_assert, kernel_sources, parse_resource_usage
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ['yue_cnet_set_pairs', 'yue_cnet_walks', 'yue_cnet_set_walks', 'yue_cnet_embed', 'yue_cnet_set_embedding', 'yue_cnet_friends']
 
@@ -27,16 +29,7 @@ def test_cnet_kernels_no_scratch_lds_budget_no_float_atomics(tmp_path):
                           '-Rpass-analysis=kernel-resource-usage', '-o', str(asm), src],
                          capture_output=True, text=True, cwd=os.path.dirname(src))
     assert out.returncode == 0, out.stderr[-2000:]
-    usage, name = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r'Function Name: (\S+)', line)
-        if m:
-            name = m.group(1)
-            usage[name] = {}
-            continue
-        m = re.search(r'remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|LDS Size \[bytes/block\]): (\d+)', line)
-        if m and name:
-            usage[name][m.group(1)] = int(m.group(2))
+    usage = parse_resource_usage(out.stderr)
     kernels = {fn: u for fn, u in usage.items() if 'k_cnet_' in fn}
     # prefix, walk, count, embed_init, embed_round<1>, embed_round<2>, embed_apply, norms, friends
     assert len(kernels) == 9, sorted(usage)
@@ -48,4 +41,7 @@ def test_cnet_kernels_no_scratch_lds_budget_no_float_atomics(tmp_path):
     text = open(str(asm)).read()
     assert not re.search(r'atomic_(add|pk_add|min|max|fadd|fmin|fmax)_(f32|f64|pk)', text)
     assert not re.search(r'atomic_add_f|atomic_pk_add', text)
+    src_text = kernel_sources(ROOT, 'cnet_kernels.hpp')
+    assert 'wg_bitonic' in src_text
+    assert '__builtin_trap' not in src_text and not has_device_assert(src_text)
     assert 'cnet_host' in open(os.path.join(os.path.dirname(src), 'Makefile')).read().split('UNITS')[1].splitlines()[0]

@@ -6,6 +6,8 @@ import re
 import shutil
 import subprocess
 
+from helpers.resource_usage import has_device_assert, kernel_sources, parse_resource_usage
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -17,16 +19,7 @@ def test_ipf_kernel_no_scratch_lds_budget_no_float_atomics(tmp_path):
                           '-Rpass-analysis=kernel-resource-usage', '-o', str(asm), src],
                          capture_output=True, text=True, cwd=os.path.dirname(src))
     assert out.returncode == 0, out.stderr[-2000:]
-    usage, name = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r'Function Name: (\S+)', line)
-        if m:
-            name = m.group(1)
-            usage[name] = {}
-            continue
-        m = re.search(r'remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|LDS Size \[bytes/block\]): (\d+)', line)
-        if m and name:
-            usage[name][m.group(1)] = int(m.group(2))
+    usage = parse_resource_usage(out.stderr)
     kernels = {fn: u for fn, u in usage.items() if 'k_ipf_' in fn}
     assert len(kernels) == 1, sorted(usage)
     for fn, u in kernels.items():
@@ -38,5 +31,6 @@ def test_ipf_kernel_no_scratch_lds_budget_no_float_atomics(tmp_path):
     assert 'global_atomic_umax_x2' in atomics, atomics                      # the level-2 / level-3 64-bit integer max
     assert not [a for a in atomics if re.search(r'f32|f64|bf16|pk_add|cmpswap', a)], atomics
     assert 's_trap' not in text
-    src_text = open(os.path.join(ROOT, 'yue_amd', 'csrc', 'ipf_kernels.hpp')).read()
-    assert '__builtin_trap' not in src_text and 'assert(' not in src_text
+    src_text = kernel_sources(ROOT, 'ipf_kernels.hpp')
+    assert 'wg_reform' in src_text
+    assert '__builtin_trap' not in src_text and not has_device_assert(src_text)

@@ -17,6 +17,7 @@
 #pragma once
 #include "bpr_device.hpp"
 #include "counter_hash.hpp"
+#include "wg_rank.hpp"
 
 #include <climits>
 
@@ -339,6 +340,7 @@ constexpr int kCnetFrQ = 8;                // query rows per workgroup
 constexpr int kCnetFrTile = 64;            // candidate rows per tile
 constexpr int kCnetFrList = 256;           // running top-K + appended candidates per query
 constexpr int kCnetFrStride = kCnetMaxDim + 1;
+static_assert((kCnetFrList & (kCnetFrList - 1)) == 0 && kCnetFrList >= kCnetMaxK + kCnetFrTile, "running top-K + one tile of appends");
 
 struct CnetFriendsArgs {
     int64_t m, nnet;
@@ -361,8 +363,6 @@ __global__ void k_cnet_norms(CnetFriendsArgs a) {
     a.norm[u] = s;
     for (int r = 0; r < a.K; ++r) { a.friends[u * a.K + r] = -1; a.sims[u * a.K + r] = 0.0; }
 }
-
-__device__ inline bool cnet_better(double s1, int32_t v1, double s2, int32_t v2) { return s1 > s2 || (s1 == s2 && v1 < v2); }
 
 // Workgroup b ranks the query users net[8b .. 8b + 8) against every network user, 64 candidate rows at a time.  Thread t
 // takes candidate t & 63 for the two queries 2 (t >> 6), + 1.  cosine = dot / sqrt(n_a n_b) in fp64 (tool/qmath.py:36-45;
@@ -388,27 +388,20 @@ __global__ __launch_bounds__(kCnetFrThreads) void k_cnet_friends(CnetFriendsArgs
     if (tid < kCnetFrQ) { qn[tid] = tid < nq ? a.norm[a.net[q0 + tid]] : 0.0; nl[tid] = 0; nc[tid] = 0; }
     __syncthreads();
 
-    auto merge = [&]() {                   // all threads; sorts the eight lists at once (the xor partners stay inside a list)
+    double *fs = &ls[0][0];                // the eight lists back to back, by flat index
+    int32_t *fi = &li[0][0];
+    auto less = [&](int x, int y) { return wg_before(fs[x], fi[x], fs[y], fi[y]); };
+    auto swap = [&](int x, int y) {
+        const double s = fs[x]; fs[x] = fs[y]; fs[y] = s;
+        const int32_t v = fi[x]; fi[x] = fi[y]; fi[y] = v;
+    };
+    auto merge = [&]() {                   // all threads; sorts the eight lists at once
         for (int x = tid; x < kCnetFrQ * kCnetFrList; x += kCnetFrThreads) {
             const int q = x / kCnetFrList, i = x % kCnetFrList;
             if (i >= nl[q] + nc[q]) { ls[q][i] = -INFINITY; li[q][i] = INT_MAX; }
         }
         __syncthreads();
-        for (int k = 2; k <= kCnetFrList; k <<= 1)
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                for (int x = tid; x < kCnetFrQ * kCnetFrList; x += kCnetFrThreads) {
-                    const int q = x / kCnetFrList, i = x % kCnetFrList, ixj = i ^ j;
-                    if (ixj > i) {
-                        const bool up = (i & k) == 0;
-                        const bool sw = up ? cnet_better(ls[q][ixj], li[q][ixj], ls[q][i], li[q][i]) : cnet_better(ls[q][i], li[q][i], ls[q][ixj], li[q][ixj]);
-                        if (sw) {
-                            const double s = ls[q][i]; ls[q][i] = ls[q][ixj]; ls[q][ixj] = s;
-                            const int32_t v = li[q][i]; li[q][i] = li[q][ixj]; li[q][ixj] = v;
-                        }
-                    }
-                }
-                __syncthreads();
-            }
+        wg_bitonic<kCnetFrThreads>(kCnetFrQ, kCnetFrList, less, swap);
         if (tid < kCnetFrQ) { const int tot = nl[tid] + nc[tid]; nl[tid] = tot < K ? tot : K; nc[tid] = 0; }
         __syncthreads();
     };
@@ -441,7 +434,7 @@ __global__ __launch_bounds__(kCnetFrThreads) void k_cnet_friends(CnetFriendsArgs
             if (q >= nq || v < 0 || v == a.net[q0 + q]) continue;
             const double den = sqrt(qn[q] * tn[c]);
             const double s = den == 0.0 ? 0.0 : (h ? d1 : d0) / den;
-            if (nl[q] < K || cnet_better(s, v, ls[q][K - 1], li[q][K - 1])) {
+            if (nl[q] < K || wg_before(s, v, ls[q][K - 1], li[q][K - 1])) {
                 const int at = nl[q] + atomicAdd(&nc[q], 1);
                 ls[q][at] = s; li[q][at] = v;
             }

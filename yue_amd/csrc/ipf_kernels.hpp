@@ -11,6 +11,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "wg_rank.hpp"
+
 #include <cstdint>
 
 namespace yue {
@@ -18,6 +20,7 @@ namespace yue {
 constexpr int kIpfThreads = 256;
 constexpr int kIpfMaxN = 100;                   // top-N of the ranking (the reference's own cap)
 constexpr int kIpfSel = 1024;                   // running top-N + appended candidates of the selection (LDS)
+static_assert((kIpfSel & (kIpfSel - 1)) == 0 && kIpfSel >= kIpfMaxN + kIpfThreads, "running top-N + one batch of appends");
 constexpr int kIpfKBits = 18;                   // distinct items of one user's list  < 2^18 (level-1 index k, level-3 index j)
 constexpr int kIpfPosBits = 26;                 // length of one holder list (duplicates counted for sessions) < 2^26
 constexpr unsigned long long kIpfUnreached = ~0ull;   // ins[] of an item no path has reached
@@ -62,35 +65,6 @@ __device__ inline void ipf_sync() {
 
 __device__ inline unsigned long long ipf_ld(const unsigned long long *p) {   // served by L2 (written by atomics)
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// inclusive scan of one value per thread over the workgroup; returns the total (all threads)
-__device__ inline int64_t ipf_scan(int64_t x, int64_t *incl) {
-    const int t = threadIdx.x;
-    incl[t] = x;
-    __syncthreads();
-    for (int off = 1; off < kIpfThreads; off <<= 1) {
-        const int64_t y = t >= off ? incl[t - off] : 0;
-        __syncthreads();
-        incl[t] += y;
-        __syncthreads();
-    }
-    return incl[kIpfThreads - 1];
-}
-
-// flattened position f of the concatenated segments -> segment index (smallest j with incl[j] > f)
-__device__ inline int ipf_segment_of(const int64_t *incl, int64_t f) {
-    int lo = 0, hi = kIpfThreads - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (incl[mid] > f) hi = mid; else lo = mid + 1;
-    }
-    return lo;
-}
-
-// (score desc, insertion asc): a strict total order (insertion keys are distinct)
-__device__ inline bool ipf_before(double s1, unsigned long long i1, double s2, unsigned long long i2) {
-    return s1 > s2 || (s1 == s2 && i1 < i2);
 }
 
 // One workgroup per slot; it ranks users[q] for q = blockIdx.x, + gridDim.x, ...  Per query the four paths run in order:
@@ -145,9 +119,9 @@ __global__ __launch_bounds__(kIpfThreads) void k_ipf_rank(IpfArgs a) {
                     len = h_ptr[it + 1] - beg;
                 }
                 seg_beg[tid] = beg;
-                const int64_t total = ipf_scan(len, incl);
+                const int64_t total = wg_scan<kIpfThreads>(len, incl);
                 for (int64_t f = tid; f < total; f += kIpfThreads) {
-                    const int s = ipf_segment_of(incl, f);
+                    const int s = wg_segment_of<kIpfThreads>(incl, f);
                     const int64_t e = seg_beg[s] + (f - (s ? incl[s - 1] : 0));
                     const int32_t b = h_users[e];
                     if (exclude_u && b == u) continue;
@@ -185,9 +159,9 @@ __global__ __launch_bounds__(kIpfThreads) void k_ipf_rank(IpfArgs a) {
                         seg_val[tid] = r2[b] * W2[b];
                     }
                     seg_beg[tid] = beg;
-                    const int64_t total = ipf_scan(len, incl);
+                    const int64_t total = wg_scan<kIpfThreads>(len, incl);
                     for (int64_t f = tid; f < total; f += kIpfThreads) {
-                        const int s = ipf_segment_of(incl, f);
+                        const int s = wg_segment_of<kIpfThreads>(incl, f);
                         const int64_t j = f - (s ? incl[s - 1] : 0);
                         const int32_t c = l3_items[seg_beg[s] + j];
                         const unsigned long long k3 = seg_key[s];
@@ -225,32 +199,14 @@ __global__ __launch_bounds__(kIpfThreads) void k_ipf_rank(IpfArgs a) {
             for (int64_t e = a.u_ptr[u] + tid; e < a.u_ptr[u + 1]; e += kIpfThreads) key3[a.u_items[e]] = 1ull;
             if (tid == 0) { nl = 0; nc = 0; }
             ipf_sync();
-            auto less = [&](int x, int y) { return ipf_before(ss[x], si[x], ss[y], si[y]); };
-            auto merge = [&]() {
-                __syncthreads();
-                const int tot = nl + nc;
-                int P2 = 1;
-                while (P2 < tot) P2 <<= 1;
-                for (int i = tot + tid; i < P2; i += kIpfThreads) { ss[i] = -1.0; si[i] = kIpfUnreached; sc[i] = -1; }   // scores are >= 0
-                __syncthreads();
-                for (int k = 2; k <= P2; k <<= 1)
-                    for (int jj = k >> 1; jj > 0; jj >>= 1) {
-                        for (int i = tid; i < P2; i += kIpfThreads) {
-                            const int ixj = i ^ jj;
-                            if (ixj > i) {
-                                const bool up = (i & k) == 0;
-                                if (up ? less(ixj, i) : less(i, ixj)) {
-                                    const double s = ss[i]; ss[i] = ss[ixj]; ss[ixj] = s;
-                                    const unsigned long long w = si[i]; si[i] = si[ixj]; si[ixj] = w;
-                                    const int32_t c = sc[i]; sc[i] = sc[ixj]; sc[ixj] = c;
-                                }
-                            }
-                        }
-                        __syncthreads();
-                    }
-                if (tid == 0) { nl = tot < N ? tot : N; nc = 0; }
-                __syncthreads();
+            auto less = [&](int x, int y) { return wg_before(ss[x], si[x], ss[y], si[y]); };
+            auto swap = [&](int x, int y) {
+                const double s = ss[x]; ss[x] = ss[y]; ss[y] = s;
+                const unsigned long long w = si[x]; si[x] = si[y]; si[y] = w;
+                const int32_t c = sc[x]; sc[x] = sc[y]; sc[y] = c;
             };
+            auto pad = [&](int i) { ss[i] = -1.0; si[i] = kIpfUnreached; sc[i] = -1; };   // scores are >= 0
+            auto merge = [&]() { wg_reform<kIpfThreads>(nl, nc, N, pad, less, swap); };
             for (int t0 = 0; t0 < items; t0 += kIpfThreads) {
                 const int occupied = nl + nc;
                 __syncthreads();
@@ -261,7 +217,7 @@ __global__ __launch_bounds__(kIpfThreads) void k_ipf_rank(IpfArgs a) {
                     if (ipf_ld(&key3[c]) == 0ull) {
                         const double s = score[c];
                         const unsigned long long w = ins[c];
-                        if (nl < N || ipf_before(s, w, ss[N - 1], si[N - 1])) {
+                        if (nl < N || wg_before(s, w, ss[N - 1], si[N - 1])) {
                             const int at = nl + atomicAdd(&nc, 1);
                             ss[at] = s; si[at] = w; sc[at] = c;
                         }

@@ -6,6 +6,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "wg_rank.hpp"
+
 #include <climits>
 #include <cstdint>
 
@@ -17,7 +19,11 @@ constexpr int kKnnMaxN = 100;          // top-N of the ranking (the reference's 
 constexpr int kKnnRange = 4096;        // candidate users counted per pass of k_knn_neighbors (LDS counters)
 constexpr int kKnnSortCap = 2048;      // running top-K + appended candidates of k_knn_neighbors
 constexpr int kKnnGather = 2048;       // (item, rank) entries gathered per chunk of k_knn_topn
-constexpr int kKnnSel = 4096;          // running top-N + one chunk's scored items (>= kKnnMaxN + kKnnGather, a power of two)
+constexpr int kKnnSel = 4096;          // running top-N + one chunk's scored items
+static_assert(kKnnMaxK <= 256, "the neighbour's rank travels in 8 bits of the gather key");
+static_assert((kKnnSortCap & (kKnnSortCap - 1)) == 0 && kKnnSortCap >= kKnnMaxK + kKnnThreads, "running top-K + one batch of appends");
+static_assert((kKnnGather & (kKnnGather - 1)) == 0, "a chunk is padded to a power of two inside gkey");
+static_assert((kKnnSel & (kKnnSel - 1)) == 0 && kKnnSel >= kKnnMaxN + kKnnGather, "running top-N + one chunk's scored items");
 
 struct KnnArgs {
     int64_t m, n;
@@ -66,52 +72,6 @@ __device__ inline int64_t knn_gallop(const int32_t *a, int64_t cur, int64_t end,
     return hi;
 }
 
-// inclusive scan of one value per thread over the workgroup; returns the total (all threads)
-__device__ inline int knn_scan(int x, int *incl) {
-    const int t = threadIdx.x;
-    incl[t] = x;
-    __syncthreads();
-    for (int off = 1; off < kKnnThreads; off <<= 1) {
-        const int y = t >= off ? incl[t - off] : 0;
-        __syncthreads();
-        incl[t] += y;
-        __syncthreads();
-    }
-    return incl[kKnnThreads - 1];
-}
-
-// flattened position f of the concatenated segments -> segment index (smallest j with incl[j] > f)
-__device__ inline int knn_segment_of(const int *incl, int f) {
-    int lo = 0, hi = kKnnThreads - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (incl[mid] > f) hi = mid; else lo = mid + 1;
-    }
-    return lo;
-}
-
-// bitonic sort of P (a power of two) LDS entries, ascending by less(i, j); ends with a barrier
-template <class Less, class Swap>
-__device__ inline void knn_bitonic(int P, Less less, Swap swap) {
-    for (int k = 2; k <= P; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = threadIdx.x; i < P; i += kKnnThreads) {
-                const int ixj = i ^ j;
-                if (ixj > i) {
-                    const bool up = (i & k) == 0;
-                    if (up ? less(ixj, i) : less(i, ixj)) swap(i, ixj);
-                }
-            }
-            __syncthreads();
-        }
-}
-
-__device__ inline int knn_pow2(int x) {
-    int p = 1;
-    while (p < x) p <<= 1;
-    return p;
-}
-
 // One workgroup per row user u.  Candidates v are counted in passes of `range` consecutive user ids: for every item of
 // A_u, the part of its posting list inside the pass is walked (cursor kept across passes) and c[v] += 1 in LDS; the
 // first touch of a counter appends v to a touched list, so extraction and clearing cost the distinct candidates.  A
@@ -144,16 +104,8 @@ __global__ __launch_bounds__(kKnnThreads) void k_knn_neighbors(KnnArgs a) {
         t = sc[x]; sc[x] = sc[y]; sc[y] = t;
         t = sU[x]; sU[x] = sU[y]; sU[y] = t;
     };
-    auto merge = [&]() {
-        __syncthreads();
-        const int tot = nl + nc;
-        const int P = knn_pow2(tot);
-        for (int i = tot + tid; i < P; i += kKnnThreads) { sv[i] = INT_MAX; sc[i] = 0; sU[i] = 1; }   // sim 0: behind every candidate
-        __syncthreads();
-        knn_bitonic(P, less, swap);
-        if (tid == 0) { nl = tot < K ? tot : K; nc = 0; }
-        __syncthreads();
-    };
+    auto pad = [&](int i) { sv[i] = INT_MAX; sc[i] = 0; sU[i] = 1; };   // sim 0: behind every candidate
+    auto merge = [&]() { wg_reform<kKnnThreads>(nl, nc, K, pad, less, swap); };
 
     for (int64_t lo = 0; lo < a.m; lo += a.range) {
         const int64_t hi = lo + a.range < a.m ? lo + a.range : a.m;
@@ -170,9 +122,9 @@ __global__ __launch_bounds__(kKnnThreads) void k_knn_neighbors(KnnArgs a) {
                 a.cursor[rb + jj] = p;
             }
             seg_beg[tid] = beg;
-            const int total = knn_scan(len, incl);
+            const int total = wg_scan<kKnnThreads>(len, incl);
             for (int f = tid; f < total; f += kKnnThreads) {
-                const int j = knn_segment_of(incl, f);
+                const int j = wg_segment_of<kKnnThreads>(incl, f);
                 const int excl = j ? incl[j - 1] : 0;
                 const int idx = (int)(a.i_users[seg_beg[j] + (f - excl)] - lo);
                 if (atomicAdd(&cnt[idx], 1u) == 0u) touched[atomicAdd(&nt, 1)] = idx;
@@ -241,7 +193,7 @@ __global__ __launch_bounds__(kKnnThreads) void k_knn_topn(KnnArgs a) {
         cur = a.u_ptr[v];
         end = a.u_ptr[v + 1];
     }
-    const int total_all = knn_scan((int)(end - cur < a.gather + 1 ? end - cur : a.gather + 1), incl);   // clamped: no overflow
+    const int total_all = wg_scan<kKnnThreads>((int)(end - cur < a.gather + 1 ? end - cur : a.gather + 1), incl);   // clamped: no overflow
     const int64_t width = total_all <= a.gather ? a.n : (int64_t)(a.gather / kp);
     if (tid == 0) {
         nl = 0; nc = 0;
@@ -255,7 +207,8 @@ __global__ __launch_bounds__(kKnnThreads) void k_knn_topn(KnnArgs a) {
         const unsigned long long k = gkey[x]; gkey[x] = gkey[y]; gkey[y] = k;
         const int32_t c = gcnt[x]; gcnt[x] = gcnt[y]; gcnt[y] = c;
     };
-    auto sless = [&](int x, int y) { return ss[x] > ss[y] || (ss[x] == ss[y] && si[x] < si[y]); };
+    auto spad = [&](int f) { ss[f] = -1.0; si[f] = INT_MAX; };   // scores are > 0
+    auto sless = [&](int x, int y) { return wg_before(ss[x], si[x], ss[y], si[y]); };
     auto sswap = [&](int x, int y) {
         const double s = ss[x]; ss[x] = ss[y]; ss[y] = s;
         const int32_t i = si[x]; si[x] = si[y]; si[y] = i;
@@ -270,18 +223,18 @@ __global__ __launch_bounds__(kKnnThreads) void k_knn_topn(KnnArgs a) {
             seg_beg[tid] = cur;
             cur = p;
         }
-        const int total = knn_scan(len, incl);          // <= gather: kp * width entries at most
+        const int total = wg_scan<kKnnThreads>(len, incl);          // <= gather: kp * width entries at most
         for (int f = tid; f < total; f += kKnnThreads) {
-            const int r = knn_segment_of(incl, f);
+            const int r = wg_segment_of<kKnnThreads>(incl, f);
             const int excl = r ? incl[r - 1] : 0;
             const int64_t pos = seg_beg[r] + (f - excl);
             gkey[f] = ((unsigned long long)(uint32_t)a.u_items[pos] << 8) | (unsigned)r;
             gcnt[f] = a.u_counts[pos];
         }
-        const int P = knn_pow2(total);
+        const int P = wg_pow2(total);
         for (int f = total + tid; f < P; f += kKnnThreads) gkey[f] = ~0ull;
         __syncthreads();
-        knn_bitonic(P, gless, gswap);
+        wg_bitonic<kKnnThreads>(1, P, gless, gswap);
         for (int f = tid; f < total; f += kKnnThreads) {
             const unsigned long long item = gkey[f] >> 8;
             if (f > 0 && (gkey[f - 1] >> 8) == item) continue;
@@ -303,14 +256,7 @@ __global__ __launch_bounds__(kKnnThreads) void k_knn_topn(KnnArgs a) {
             ss[s] = sum / den;
             si[s] = (int32_t)item;
         }
-        __syncthreads();
-        const int tot = nl + nc;
-        const int Q = knn_pow2(tot);
-        for (int f = tot + tid; f < Q; f += kKnnThreads) { ss[f] = -1.0; si[f] = INT_MAX; }   // scores are > 0
-        __syncthreads();
-        knn_bitonic(Q, sless, sswap);
-        if (tid == 0) { nl = tot < N ? tot : N; nc = 0; }
-        __syncthreads();
+        wg_reform<kKnnThreads>(nl, nc, N, spad, sless, sswap);
     }
     for (int r = tid; r < N; r += kKnnThreads) {
         const bool have = r < nl;
